@@ -2,6 +2,7 @@
 Gaussians, 1920x1080, SH degree 3), per-camera data parallel over N GPUs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config m2|m3|m1]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 One step = render one camera per rank through the HIP hot path (projection,
@@ -9,13 +10,21 @@ SH, isect + sort, rasterize), 0.8*L1 + 0.2*(1-SSIM) loss, backward, RCCL
 all-reduce of the Gaussian gradients (N > 1), DefaultStrategy statistics and
 Adam (see gsplat_hip/train_step.py).  Inputs are resident in HBM.
 
-Rank 0 prints one JSON line with the driver's contract plus
+A plain run sets up, warms up, times the K steps and has rank 0 print one JSON
+line with the driver's contract (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes what the timed steps returned to their caller,
+each step's loss, as DIR/loss.npy (the last step's last).  --full adds, in
+runs of their own around the timed region,
   roofline:     rasterize_to_pixels fwd -- algorithmic bytes per launch /
-                mean HIP-event duration of that launch in the timed region
-  cpu_baseline: the numpy oracle's train step on the host (bounded sample).
+                mean HIP-event duration of that launch (plus the rocprofv3
+                PMC child runs behind roofline.traffic)
+  cpu_baseline: the numpy oracle's train step on the host (bounded sample)
+  config.dp:    at N > 1 the replicated data-parallel scheme, a second timed
+                region after the main one.
 """
 
 import argparse
+import collections
 import json
 import math
 import os
@@ -48,6 +57,7 @@ MODEL = {"m5": "2dgs"}
 # steps // 2)
 DENSIFY = {"m3"}
 REFINE_AT = 3100
+LOSS_KEEP = 4096  # losses of the last timed steps that --dump-outputs writes (GraphStep.LOSS_RING)
 
 
 def parse():
@@ -56,11 +66,22 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="m2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of "
+                         "their own: the rasterizer rooflines (per-kernel HIP-event times over "
+                         "eager steps, algorithmic bytes, rocprofv3 PMC child runs), the CPU "
+                         "baseline and, at N>1, the data-parallel second timed region")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they returned to their caller, the "
+                         "loss of each (at most the last 4096, the last step's last), as "
+                         "DIR/loss.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-tile-stride", type=int, default=0,
                     help="rasterize every k-th tile in the CPU baseline (0: auto)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the rocprofv3 PMC child runs that measure roofline.traffic")
+                    help="with --full: skip the rocprofv3 PMC child runs that measure "
+                         "roofline.traffic")
     ap.add_argument("--eager", action="store_true",
                     help="issue every launch from the host each step instead of replaying "
                          "the step captured as a HIP graph")
@@ -90,7 +111,7 @@ def parse():
                          "recorded from their own renders (exchanges as device copies, no "
                          "xGMI time; measurement only)")
     ap.add_argument("--no-dp-phase", action="store_true",
-                    help="at N>1: skip the second timed region that runs the replicated "
+                    help="with --full at N>1: skip the second timed region that runs the replicated "
                          "per-camera data-parallel scheme (north_star's) after the default "
                          "Gaussian-sharded one (config.dp)")
     ap.add_argument("--dp-phase", action="store_true",
@@ -254,6 +275,8 @@ def main():
     cpu_pool = None
     if world > 1:
         args.no_cpu_baseline = True  # the CPU baseline is an N=1 measurement
+    if not args.full:
+        args.no_cpu_baseline = args.no_traffic = True  # a plain run: the timed steps only
     if rank == 0 and not args.no_cpu_baseline and not args.probe:
         # the CPU baseline's worker processes start before this process
         # touches the GPU (spawned interpreters running numpy only)
@@ -277,7 +300,7 @@ def main():
     pg_kw = {}
     if args.watchdog_s > 0:
         pg_kw["timeout"] = datetime.timedelta(seconds=args.watchdog_s)
-    dp_phase = (world > 1 and not dp_path and not args.no_dp_phase) or (
+    dp_phase = (world > 1 and not dp_path and args.full and not args.no_dp_phase) or (
         args.dp_phase and world == 1 and not dp_path and not emu_world and not args.probe)
     if world > 1:
         torch.cuda.set_device(local)
@@ -368,28 +391,161 @@ def main():
         torch.cuda.synchronize()
         return
 
-    timers = _wrapper.enable_kernel_timers(True)
+    timers = _wrapper.enable_kernel_timers(True) if args.full else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    # what the timed steps return, for --dump-outputs: the last LOSS_KEEP of
+    # them (a replayed step's loss is a slot of a device ring that long)
+    losses = collections.deque(maxlen=LOSS_KEEP)
     t0 = time.perf_counter()
     for it in range(start + args.warmup, start + args.warmup + args.steps):
         beat("timed", it, tr)
-        tr.step(it)
+        losses.append(tr.step(it).detach())  # (a view: no launch)
     beat("timed sync", start + args.warmup + args.steps, tr)
     tr.sync()  # graph replays: every step's overflow check settled inside the timed region
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses)
     # (after the timed region: a failed capture falls back to eager steps)
     graphed = getattr(tr, "_graph", None) is not None
-    graph_info = None
+    graph_info = _graph_info(tr._graph) if graphed else None
+    extra = None
+    if args.full:  # (advances the trainer by a few eager steps: after the dump)
+        extra = full_figures(args, tr, timers, model, start, vm_pool, dev, W, H, beat, traffic,
+                             graphed, world)
+    result = {
+        "metric": "train-step images/sec + rasterize fwd HBM GB/s, garden 1080p, 1/2/4/8 MI355X",
+        "value": world * args.steps / elapsed,
+        "unit": "images/s",
+        "n_gpus": dist.get_world_size() if world > 1 else 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic: garden SfM points (assets/test_garden.npz crop) tiled "
+                f"{grid}x{grid}, random scales/quats/opacities, random target images",
+        "config": {"workload": desc, "gaussians": N,
+                   "gaussians_after": int(sum(tr._n_world) if gshard
+                                          else tr.params["means"].shape[0]),
+                   "first_timed_step": start + args.warmup, "width": W, "height": H,
+                   "cameras_per_rank_per_step": 1,
+                   "parallelism": (
+                       f"gshard{emu_world} emulated on one GPU: the per-rank step of rank 0 "
+                       f"(Gaussians [0::{emu_world}], its own camera, projection + SH into "
+                       f"{emu_world} cameras, rasterization with all Gaussians, per-shard Adam); "
+                       "the other ranks' exchanged rows are stand-ins recorded from their own "
+                       "renders and the exchanges are device copies of the same rows -- no "
+                       "xGMI time (measurement only)") if emu_world else (
+                       f"gshard{world}: rank r holds Gaussians [r::{world}] and renders its own "
+                       "camera; projected pairs exchanged peer to peer over RCCL/xGMI "
+                       "(rasterization(distributed=True)), per-shard Adam, no gradient "
+                       "all-reduce") if gshard else f"dp{world}" + (
+                       f" emulating the per-rank compute of dp{args.dp_emulate}: optimizer rows "
+                       f"sharded {args.dp_emulate} ways, this rank's share updated, no "
+                       "collectives executed (measurement only)" if args.dp_emulate else
+                       " (the N>1 code path on a 1-rank RCCL group: sharded Adam, "
+                       "early SH reduce-scatter)" if dp_path and world == 1 else ""),
+                   # bytes this rank sends to its peers per step (distributed.exchange_pairs:
+                   # 48 B per (Gaussian, peer camera) forward, 40 B of gradients back)
+                   "exchange_bytes_out_per_rank": (
+                       {"forward": 48 * tr.params["means"].shape[0] * (len(tr._n_world) - 1),
+                        "backward": 40 * tr.params["means"].shape[0] * (len(tr._n_world) - 1)}
+                       if gshard else None),
+                   # (the rasterizer's isect counts and the visible fractions: --full)
+                   "n_isects_mean": None, "n_eff_mean": None,
+                   "fwd_split_div": getattr(tr, "split_div", None),
+                   "termination_ratio_first_render": getattr(tr, "term_ratio", None),
+                   "visible_per_camera": None, "visible_union_8_cameras": None,
+                   "packed": False, "loss": "0.8*L1+0.2*(1-SSIM valid)",
+                   "step_issue": ("HIP graph replay of the captured step (sync-free isect, "
+                                  f"{graph_info})" if graphed else "eager launches" + (
+                                      f" (graph capture failed: {tr.graph_fallback})"
+                                      if getattr(tr, "graph_fallback", None) else "")),
+                   "optimizer": "Adam (6 groups)" + (
+                       ", each rank on its own Gaussians" if gshard else
+                       ", sharded over ranks" if dp_path else
+                       ", SH groups' step fused into the SH backward"
+                       if getattr(tr, "sh_adam_in_bwd", False) else ""),
+                   "densification": tr.densify_desc()},
+        "roofline": None if extra is None else extra["roofline"],
+        "model": model,
+        "full": args.full,
+    }
+    if extra is not None:
+        result["config"].update(extra["config"])
+    if dp_path:  # the main region IS the replicated data-parallel scheme
+        result["config"]["dp"] = {"phase": "main", "value": result["value"],
+                                  "ms_per_step": result["ms_per_step"],
+                                  "step_issue": result["config"]["step_issue"]}
+    if rank == 0 and not args.no_cpu_baseline:
+        # after the timed region; the other ranks wait at the barrier below
+        if wd is not None:
+            wd.disarm()  # host-only work of bounded length (tens of seconds)
+        try:
+            result["cpu_baseline"] = cpu_baseline(tr, args.cpu_tile_stride, cpu_pool)
+        finally:
+            cpu_pool.close()
+        if wd is not None:
+            wd.arm(f"rank {rank} cpu baseline done")
+    if dp_phase:
+        # north_star's own multi-GPU scheme, timed in the same job after the
+        # main (Gaussian-sharded) region: replicated Gaussians, per-camera
+        # data parallelism, gradients reduce-scattered and rows all-gathered
+        # over RCCL (distributed.ShardedAdam).  A failure is recorded here
+        # without losing the main value; a hang ends the job through the
+        # watchdog, which then still delivers the main line (dp: "hung")
+        if wd is not None:
+            hung = dict(result, config=dict(result["config"], dp={
+                "error": f"hung: no progress for {args.watchdog_s:.0f} s (watchdog)"}))
+            wd.fallback(json_fd if rank == 0 else 2,
+                        json.dumps(hung) + "\n" if rank == 0 else "", 0)
+        tr.release_graph()
+        del tr
+        import gc
+        gc.collect()
+        torch.cuda.empty_cache()
+        try:
+            result["config"]["dp"] = dp_region(args, means, rgbs, vm_pool, K_pool, W, H, dev, world,
+                                               rank, start, kw, beat)
+        except Exception as e:  # noqa: BLE001 -- recorded, the main value stands
+            import traceback
+            traceback.print_exc()
+            result["config"]["dp"] = {"error": repr(e)[:400]}
+        if wd is not None:
+            wd.fallback(-1, None)
+        tr = None
+    if rank == 0:
+        os.write(json_fd, (json.dumps(result) + "\n").encode())
+    if world > 1:
+        dist.barrier()
+    if wd is not None:
+        wd.disarm()
+    if tr is not None:
+        tr.release_graph()  # settle and destroy the captured step before the process ends
+    if dist.is_initialized():
+        import gc
+        gc.collect()  # graphs that captured RCCL collectives, before the group goes
+        torch.cuda.synchronize()
+        dist.destroy_process_group()
+
+
+def full_figures(args, tr, timers, model, start, vm_pool, dev, W, H, beat, traffic, graphed,
+                 world):
+    """--full, after the timed region: the rasterizer launches' HIP-event
+    times and algorithmic bytes (the `roofline` entry of the result line) and
+    the isect / visibility figures that go into its `config`."""
+    from gsplat_hip import _wrapper
     if graphed:
         # kernel durations: a graph replay runs the same kernels as an eager
         # step, but HIP events cannot be recorded per replay -- time the
         # rasterizer launches over eager steps right after the timed region
-        graph_info = _graph_info(tr._graph)
         tr.release_graph()  # (RCCL: before destroy_process_group, GraphStep.release)
         timers = _wrapper.enable_kernel_timers(True)
         n_t = min(args.steps, 10)
@@ -478,63 +634,10 @@ def main():
 
     pf = None if traffic is None else traffic["fwd"]
     pb = None if traffic is None else traffic["bwd"]
-    result = {
-        "metric": "train-step images/sec + rasterize fwd HBM GB/s, garden 1080p, 1/2/4/8 MI355X",
-        "value": world * args.steps / elapsed,
-        "unit": "images/s",
-        "n_gpus": dist.get_world_size() if world > 1 else 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic: garden SfM points (assets/test_garden.npz crop) tiled "
-                f"{grid}x{grid}, random scales/quats/opacities, random target images",
-        "config": {"workload": desc, "gaussians": N,
-                   "gaussians_after": int(sum(tr._n_world) if gshard
-                                          else tr.params["means"].shape[0]),
-                   "first_timed_step": start + args.warmup, "width": W, "height": H,
-                   "cameras_per_rank_per_step": 1,
-                   "parallelism": (
-                       f"gshard{emu_world} emulated on one GPU: the per-rank step of rank 0 "
-                       f"(Gaussians [0::{emu_world}], its own camera, projection + SH into "
-                       f"{emu_world} cameras, rasterization with all Gaussians, per-shard Adam); "
-                       "the other ranks' exchanged rows are stand-ins recorded from their own "
-                       "renders and the exchanges are device copies of the same rows -- no "
-                       "xGMI time (measurement only)") if emu_world else (
-                       f"gshard{world}: rank r holds Gaussians [r::{world}] and renders its own "
-                       "camera; projected pairs exchanged peer to peer over RCCL/xGMI "
-                       "(rasterization(distributed=True)), per-shard Adam, no gradient "
-                       "all-reduce") if gshard else f"dp{world}" + (
-                       f" emulating the per-rank compute of dp{args.dp_emulate}: optimizer rows "
-                       f"sharded {args.dp_emulate} ways, this rank's share updated, no "
-                       "collectives executed (measurement only)" if args.dp_emulate else
-                       " (the N>1 code path on a 1-rank RCCL group: sharded Adam, "
-                       "early SH reduce-scatter)" if dp_path and world == 1 else ""),
-                   # bytes this rank sends to its peers per step (distributed.exchange_pairs:
-                   # 48 B per (Gaussian, peer camera) forward, 40 B of gradients back)
-                   "exchange_bytes_out_per_rank": (
-                       {"forward": 48 * tr.params["means"].shape[0] * (len(tr._n_world) - 1),
-                        "backward": 40 * tr.params["means"].shape[0] * (len(tr._n_world) - 1)}
-                       if gshard else None),
-                   "n_isects_mean": float(np.mean(isects)), "n_eff_mean": float(np.mean(n_effs)),
-                   "fwd_split_div": getattr(tr, "split_div", None),
-                   "termination_ratio_first_render": getattr(tr, "term_ratio", None),
+    return {
+        "config": {"n_isects_mean": float(np.mean(isects)), "n_eff_mean": float(np.mean(n_effs)),
                    "visible_per_camera": per_cam_visible,
-                   "visible_union_8_cameras": union_visible,
-                   "packed": False, "loss": "0.8*L1+0.2*(1-SSIM valid)",
-                   "step_issue": ("HIP graph replay of the captured step (sync-free isect, "
-                                  f"{graph_info})" if graphed else "eager launches" + (
-                                      f" (graph capture failed: {tr.graph_fallback})"
-                                      if getattr(tr, "graph_fallback", None) else "")),
-                   "optimizer": "Adam (6 groups)" + (
-                       ", each rank on its own Gaussians" if gshard else
-                       ", sharded over ranks" if dp_path else
-                       ", SH groups' step fused into the SH backward"
-                       if getattr(tr, "sh_adam_in_bwd", False) else ""),
-                   "densification": tr.densify_desc()},
+                   "visible_union_8_cameras": union_visible},
         "roofline": {"kernel": kname, "bound": "hbm", "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": None if pf is None else pf["bytes_per_launch"],
@@ -559,62 +662,21 @@ def main():
                      "pmc_source": None if traffic is None else traffic["source"],
                      "pmc_note": None if world == 1 else "PMC passes run at N=1 only "
                                  "(per-GPU workload is the same at every N)"},
-        "model": model,
     }
-    if dp_path:  # the main region IS the replicated data-parallel scheme
-        result["config"]["dp"] = {"phase": "main", "value": result["value"],
-                                  "ms_per_step": result["ms_per_step"],
-                                  "step_issue": result["config"]["step_issue"]}
-    if rank == 0 and not args.no_cpu_baseline:
-        # after the timed region; the other ranks wait at the barrier below
-        if wd is not None:
-            wd.disarm()  # host-only work of bounded length (tens of seconds)
-        try:
-            result["cpu_baseline"] = cpu_baseline(tr, args.cpu_tile_stride, cpu_pool)
-        finally:
-            cpu_pool.close()
-        if wd is not None:
-            wd.arm(f"rank {rank} cpu baseline done")
-    if dp_phase:
-        # north_star's own multi-GPU scheme, timed in the same job after the
-        # main (Gaussian-sharded) region: replicated Gaussians, per-camera
-        # data parallelism, gradients reduce-scattered and rows all-gathered
-        # over RCCL (distributed.ShardedAdam).  A failure is recorded here
-        # without losing the main value; a hang ends the job through the
-        # watchdog, which then still delivers the main line (dp: "hung")
-        if wd is not None:
-            hung = dict(result, config=dict(result["config"], dp={
-                "error": f"hung: no progress for {args.watchdog_s:.0f} s (watchdog)"}))
-            wd.fallback(json_fd if rank == 0 else 2,
-                        json.dumps(hung) + "\n" if rank == 0 else "", 0)
-        tr.release_graph()
-        del tr
-        import gc
-        gc.collect()
-        torch.cuda.empty_cache()
-        try:
-            result["config"]["dp"] = dp_region(args, means, rgbs, vm_pool, K_pool, W, H, dev, world,
-                                               rank, start, kw, beat)
-        except Exception as e:  # noqa: BLE001 -- recorded, the main value stands
-            import traceback
-            traceback.print_exc()
-            result["config"]["dp"] = {"error": repr(e)[:400]}
-        if wd is not None:
-            wd.fallback(-1, None)
-        tr = None
-    if rank == 0:
-        os.write(json_fd, (json.dumps(result) + "\n").encode())
-    if world > 1:
-        dist.barrier()
-    if wd is not None:
-        wd.disarm()
-    if dist.is_initialized():
-        if tr is not None:
-            tr.release_graph()
-        import gc
-        gc.collect()  # graphs that captured RCCL collectives, before the group goes
-        torch.cuda.synchronize()
-        dist.destroy_process_group()
+
+
+def dump_outputs(path, losses):
+    """--dump-outputs: what the timed path returns to its caller, the loss of
+    each timed step (`losses`, in step order, the last one last), as float32
+    `path`/loss.npy.  The parameters the steps update are not written: the
+    backward sums with float atomics and Adam (eps 1e-15) turns a gradient
+    entry near zero whose sign the summation order decides into a full step,
+    so two runs of one build agree in them only for a few steps (M2, after 205
+    steps: opacities differ by up to 3.4, 12 % of them by more than 0.01; the
+    loss by 5e-7), and they cannot tell two builds apart."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"),
+            torch.stack(list(losses)).float().cpu().numpy())
 
 
 def _graph_info(g):

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${1:-bwd_attr}; mkdir -p $O
 CFG=${CFG:-m2}
 for v in ${DBGS:-0 1 5 13}; do
-  GSPLAT_HIP_DBG=$v timeout -k 10 300 python -u bench.py --config $CFG --no-cpu-baseline --no-traffic --steps 20 \
+  GSPLAT_HIP_DBG=$v timeout -k 10 300 python -u bench.py --full --config $CFG --no-cpu-baseline --no-traffic --steps 20 \
     > $O/bench_dbg$v.json 2> $O/bench_dbg$v.err || exit 2
   python -c "import json; d=json.load(open('$O/bench_dbg$v.json')); print('dbg $v', round(d['value'],1), 'fwd', round(d['roofline']['launch_ms'],4), 'bwd', round(d['roofline']['bwd']['launch_ms'],4))"
   GSPLAT_HIP_DBG=$v timeout -s KILL 120 rocprofv3 --kernel-include-regex "bwd2_kernel" \

@@ -15,7 +15,7 @@ if [ "$2" = a ]; then
     > $O/suite.log 2>&1
   rc=$?; echo "suite rc=$rc"; tail -3 $O/suite.log
   [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-  timeout -k 10 600 python -u bench.py > $O/bench_m2.json 2> $O/bench_m2.err || exit 2
+  timeout -k 10 600 python -u bench.py --full > $O/bench_m2.json 2> $O/bench_m2.err || exit 2
   line $O/bench_m2.json m2
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace_m2 -o run -- \
     /usr/bin/python3 bench.py --no-cpu-baseline --no-traffic > $O/trace_m2.log 2>&1 || exit 3
@@ -23,9 +23,9 @@ if [ "$2" = a ]; then
   head -12 $O/kstats_m2.txt
   exit $rc
 fi
-timeout -k 10 400 python -u bench.py --config m3 --no-cpu-baseline > $O/bench_m3.json 2> $O/bench_m3.err || exit 4
+timeout -k 10 400 python -u bench.py --full --config m3 --no-cpu-baseline > $O/bench_m3.json 2> $O/bench_m3.err || exit 4
 line $O/bench_m3.json m3
-timeout -k 10 400 python -u bench.py --config m5 --no-cpu-baseline > $O/bench_m5.json 2> $O/bench_m5.err || exit 5
+timeout -k 10 400 python -u bench.py --full --config m5 --no-cpu-baseline > $O/bench_m5.json 2> $O/bench_m5.err || exit 5
 line $O/bench_m5.json m5
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace_m5 -o run -- \
   /usr/bin/python3 bench.py --config m5 --no-cpu-baseline --no-traffic > $O/trace_m5.log 2>&1 || exit 6

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/${1:-m5}; mkdir -p $O
 for r in 1 2; do
-  timeout -k 10 300 python -u bench.py --config m5 --no-cpu-baseline --no-traffic --steps 30 \
+  timeout -k 10 300 python -u bench.py --full --config m5 --no-cpu-baseline --no-traffic --steps 30 \
     > $O/bench_m5_$r.json 2> $O/bench_m5_$r.err || exit 2
   python -c "import json; d=json.load(open('$O/bench_m5_$r.json')); print('m5 run $r', round(d['value'],1), round(d['ms_per_step'],4), 'fwd', round(d['roofline']['launch_ms'],4), 'bwd', round(d['roofline']['bwd']['launch_ms'],4))"
 done

@@ -9,7 +9,7 @@ for r in 1 2; do
   for c in 1 0; do
     timeout -k 10 300 python -u -c "
 import sys
-sys.argv = ['bench.py', '--config', 'm5', '--no-cpu-baseline', '--no-traffic', '--steps', '30']
+sys.argv = ['bench.py', '--full', '--config', 'm5', '--no-cpu-baseline', '--no-traffic', '--steps', '30']
 sys.path.insert(0, '.'); sys.path.insert(0, 'gsplat-triton_amd')
 import gsplat_hip.rendering as r
 r.TILE_CULL = bool($c)

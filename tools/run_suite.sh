@@ -13,7 +13,7 @@ timeout -k 10 900 python -u -m pytest $SEL -m gpu -q --maxfail=10 --timeout 200 
 rc=$?; echo "suite rc=$rc"; tail -15 $O/suite.log | grep -E "passed|failed|FAILED|Error" | head -20
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 [ -n "$NO_BENCH" ] && exit $rc
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-traffic > $O/bench_m2.json 2> $O/bench_m2.err
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-traffic > $O/bench_m2.json 2> $O/bench_m2.err
 r2=$?; echo "bench m2 rc=$r2"; [ $r2 -eq 0 ] || exit $r2
 python -c "import json; d=json.load(open('$O/bench_m2.json')); print('m2', round(d['value'],1), round(d['ms_per_step'],4), 'fwd', d['roofline']['launch_ms'], 'bwd', d['roofline']['bwd']['launch_ms'])"
 timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-traffic --dp-phase > $O/bench_dpphase.json 2> $O/bench_dpphase.err

@@ -13,7 +13,7 @@ for cfg in m2 m3; do
     for v in $VARS; do
       if [ $v = s ]; then SPL=""; DB=0; else SPL=0; DB=$v; fi
       [ $cfg = m2 ] && SPL=""
-      GSPLAT_HIP_FWD_SPLIT=$SPL GSPLAT_HIP_DBG=$DB timeout -k 10 300 python -u bench.py --config $cfg --no-cpu-baseline --no-traffic --steps 20 \
+      GSPLAT_HIP_FWD_SPLIT=$SPL GSPLAT_HIP_DBG=$DB timeout -k 10 300 python -u bench.py --full --config $cfg --no-cpu-baseline --no-traffic --steps 20 \
         > $O/bench_${cfg}_dbg${v}_$r.json 2> $O/bench_${cfg}_dbg${v}_$r.err || exit 2
       python -c "import json; d=json.load(open('$O/bench_${cfg}_dbg${v}_$r.json')); print('$cfg dbg $v run $r', round(d['value'],1), 'fwd', round(d['roofline']['launch_ms'],4), 'bwd', round(d['roofline']['bwd']['launch_ms'],4))"
     done
