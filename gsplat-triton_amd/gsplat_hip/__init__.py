@@ -21,6 +21,7 @@ from ._wrapper_indices import (
     rasterize_to_indices_in_range,
     rasterize_to_indices_in_range_2dgs,
 )
+from .losses import geometry_loss_2dgs
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
 
 __all__ = [
@@ -34,6 +35,7 @@ __all__ = [
     "rasterize_to_pixels_2dgs",
     "rasterization_2dgs",
     "depth_to_normal",
+    "geometry_loss_2dgs",
     "quat_scale_to_covar_preci",
     "compute_relocation",
     "adam",

@@ -238,6 +238,13 @@ class GraphStep:
         self.loss_ring = torch.zeros(self.LOSS_RING, dtype=torch.float32, device=dev)
         self.ring_loss = not (getattr(tr, "opacity_reg", 0.0) > 0.0 or
                               getattr(tr, "scale_reg", 0.0) > 0.0)
+        # 2DGS: the (normal_lambda, dist_lambda) of the captured step
+        # (Trainer.geometry_terms_at; part of the capture's key).  With a term
+        # active the loss is a sum formed after the photometric launch: the
+        # ring is bypassed, as with the regularisers
+        self.terms = (0.0, 0.0)
+        self.ring_now = self.ring_loss
+        self._warmed = set()  # the active-term sets a warm-up step has run for
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # sticky overflow flag
         self.ring_in = _Mapped(self.RING * self.SLOT)
         self.ring_out = _Mapped(self.RING * 4 * 8)
@@ -303,7 +310,19 @@ class GraphStep:
             dkw = dict(distributed=True, _world_cameras=(self.vm_w, self.K_w),
                        _world_counts=tr._n_world)
         grad_box = {}
-        if tr.model == "2dgs":  # Trainer.render's call, with the sync-free isect
+        terms = self.terms
+        if tr.model == "2dgs" and any(terms):
+            # Trainer.render(geometry=terms)'s call, with the sync-free isect
+            rc, ra, rn, _, rd, _, meta = rasterization_2dgs(
+                p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), self.vm, self.K,
+                tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
+                far_plane=1e10, render_mode="RGB+D", distloss=bool(terms[1]), _fusion=fusion,
+                _isect_capacity=self.capacity, _isect_status=self.status,
+                _isect_report=(self.ring_out.dev, self.slot), _camtoworlds=self.c2w,
+                _geometry=True)
+            colors = meta["_rgbd"] = rc
+            meta["_geometry"] = (rn, ra, rd)
+        elif tr.model == "2dgs":  # Trainer.render's call, with the sync-free isect
             rc, _, _, _, _, _, meta = rasterization_2dgs(
                 p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), self.vm, self.K,
                 tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
@@ -332,10 +351,13 @@ class GraphStep:
             from . import distributed as gdist
             vote = dist.all_reduce(self.status, op=dist.ReduceOp.MAX, async_op=True,
                                    group=gdist.current_capture_group())
-        loss = tr._regularise(l1_ssim_loss(
+        loss = l1_ssim_loss(
             colors, tr.targets, tr.ssim_lambda, gt_index=self.cam,
-            _out_ring=(self.loss_ring, self.seq) if self.ring_loss else None,
-            _channels=3 if tr.model == "2dgs" else None))
+            _out_ring=(self.loss_ring, self.seq) if self.ring_now else None,
+            _channels=3 if tr.model == "2dgs" else None)
+        if any(terms):
+            loss = loss + tr.geometry_loss(meta, self.K, terms)
+        loss = tr._regularise(loss)
         if vote is not None:
             vote.wait()
             _lib.call("gsplat_hip_status_to_ring", self.status.data_ptr(), self.ring_out.dev,
@@ -424,14 +446,19 @@ class GraphStep:
         if self.dp:
             tr.opt.wait()  # an eager step's deferred all-gathers
         torch.cuda.synchronize(self.dev)
+        self.ring_now = self.ring_loss and not any(self.terms)
         try:
             # warm-up on a side stream (torch's capture recipe) as a VOID
             # step: the flag makes every state update a no-op.  Only before
             # the first capture: a re-capture (a refine's new tensors, the SH
             # degree) runs code that has run before, and the warm-up would
-            # cost a whole extra step per refine
+            # cost a whole extra step per refine.  The first capture with a
+            # geometry term runs new kernels (the general surfel rasterizer,
+            # the geometry loss): warmed up once per set of active terms
             self.status.fill_(1)
-            if self.recaptures == 0:
+            active = tuple(bool(x) for x in self.terms)
+            if self.recaptures == 0 or active not in self._warmed:
+                self._warmed.add(active)
                 s = torch.cuda.Stream(device=self.dev)
                 s.wait_stream(torch.cuda.current_stream(self.dev))
                 with torch.cuda.stream(s):
@@ -524,12 +551,14 @@ class GraphStep:
         if tr.max_steps:
             tr._set_means_lr(lrs[0])
 
-    def _key_of(self, deg, stats):
+    def _key_of(self, deg, stats, terms=None):
         """What a capture is valid for: SH degree, the parameter tensors
-        (their generation: a refine replaces them) and whether the step
-        accumulates the strategy statistics."""
+        (their generation: a refine replaces them), whether the step
+        accumulates the strategy statistics, and the active geometry terms
+        (2DGS normal / distortion lambdas; None: the current capture's)."""
         tr = self.tr
-        return (deg, tr.params["means"].shape[0], getattr(tr, "_param_gen", 0), stats)
+        return (deg, tr.params["means"].shape[0], getattr(tr, "_param_gen", 0), stats,
+                self.terms if terms is None else tuple(terms))
 
     def _stats_at(self, it):
         st = self.tr.strategy
@@ -541,7 +570,8 @@ class GraphStep:
         tr = self.tr
         deg = tr.sh_degree_at(it)
         stats = self._stats_at(it)
-        key = self._key_of(deg, stats)
+        terms = tr.geometry_terms_at(it)
+        key = self._key_of(deg, stats, terms)
         if self.failed is not None:
             raise GraphCaptureError(self.failed)
         if self.graph is None or key != self.key:
@@ -554,6 +584,7 @@ class GraphStep:
                 self.capacity = max(self.capacity,
                                     int(math.ceil(self.capacity * key[1] / self.key[1])))
             self.graph = None  # the old capture's pool holds the old tensors
+            self.terms = terms
             self._capture(deg, stats)
         if not self.vote:
             self._check(block=len(self.pending) >= self.lag)
@@ -581,7 +612,7 @@ class GraphStep:
         self._fill(it, slot)
         self.graph.replay()
         self.tr.opt.step_count += 1
-        if self.ring_loss:
+        if self.ring_now:
             ret = self.loss_ring[k % self.LOSS_RING]
         elif ret is None:
             # (detached: a clone would keep the captured step's autograd
@@ -634,6 +665,7 @@ class GraphStep:
         # the redo steps take the voided steps' sequence numbers, so each
         # step's loss lands in the slot (or tensor) already returned for it
         self.issued = redo[0][1]
+        self.terms = tr.geometry_terms_at(redo[0][0])
         try:
             self._capture(tr.sh_degree_at(redo[0][0]), self._stats_at(redo[0][0]))
         except GraphCaptureError as e:

@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from ._wrapper import _ptr, _stream
+from ._wrapper import _dev_check, _f32c, _ptr, _stream
 
 
 class _L1SSIM(torch.autograd.Function):
@@ -173,6 +173,136 @@ def l1_ssim_loss(img, gt, ssim_lambda=0.2, fused=None, gt_index=None, _out_ring=
     if fused and img.dim() == 4 and img.shape[-1] in (1, 3):
         return _L1SSIMLossFused.apply(img, gt, float(ssim_lambda))
     return _L1SSIMLoss.apply(img, gt, float(ssim_lambda))
+
+
+class _GeometryLoss2DGS(torch.autograd.Function):
+    """normal_lambda * mean(1 - <R n, alpha n_d>) + dist_lambda * mean(distort)
+    in one reduction launch (plus a one-workgroup finish) forward and one
+    launch backward (csrc/geom_loss.hip): the normals of the depth are formed
+    in registers both ways, no torch pass and no [H,W,3] intermediate."""
+
+    @staticmethod
+    def forward(ctx, normals, depths, alphas, camtoworlds, Ks, distort, nl, dl, world, z_depth,
+                depth_image):
+        # depth_image: `depths` is a contiguous [C,H,W,D] render whose last
+        # channel is the depth; its gradient is image-shaped (zeros elsewhere)
+        do_n, do_d = nl != 0.0, dl != 0.0
+        if not do_n:
+            normals = depths = alphas = None
+        if not do_d:
+            distort = None
+        _dev_check(normals, depths, alphas, camtoworlds, Ks, distort)
+        lead = normals if do_n else distort
+        assert lead.dim() == 4, lead.shape
+        C, H, W = lead.shape[:3]
+        dev = lead.device
+        ps, d_ptr = 1, 0
+        if do_n:
+            assert normals.shape == (C, H, W, 3), normals.shape
+            assert alphas.shape == (C, H, W, 1), alphas.shape
+            assert camtoworlds.shape == (C, 4, 4) and Ks.shape == (C, 3, 3), \
+                (camtoworlds.shape, Ks.shape)
+            normals, alphas = _f32c(normals), _f32c(alphas)
+            camtoworlds, Ks = _f32c(camtoworlds), _f32c(Ks)
+            if depth_image:
+                assert depths.shape[:3] == (C, H, W) and depths.dtype == torch.float32 \
+                    and depths.is_contiguous(), depths.shape
+                ps = depths.shape[3]
+                d_ptr = depths.data_ptr() + 4 * (ps - 1)
+            else:
+                assert depths.shape == (C, H, W, 1), depths.shape
+                # the last channel of an RGB+D render is read in place (pixel stride)
+                ps = depths.stride(2)
+                if not (depths.dtype == torch.float32 and ps >= 1 and depths.stride(1) == W * ps
+                        and depths.stride(0) == H * W * ps):
+                    depths, ps = _f32c(depths), 1
+                d_ptr = depths.data_ptr()
+        if do_d:
+            assert distort.shape == (C, H, W, 1), distort.shape
+            distort = _f32c(distort)
+        ws = torch.empty(max(int(_lib.query("gsplat_hip_geom_loss_2dgs_workspace_bytes",
+                                            C, H, W)), 4), dtype=torch.uint8, device=dev)
+        out = torch.empty(3, device=dev)
+        _lib.call("gsplat_hip_geom_loss_2dgs_fwd", C, H, W, _ptr(normals), d_ptr, int(ps),
+                  _ptr(alphas), _ptr(distort), _ptr(camtoworlds), _ptr(Ks), int(bool(z_depth)),
+                  int(bool(world)), ctypes.c_float(nl), ctypes.c_float(dl), _ptr(out), _ptr(ws),
+                  _stream())
+        ctx.save_for_backward(normals, depths, alphas, camtoworlds, Ks)
+        ctx.cfg = (C, H, W, int(ps), float(nl), float(dl), bool(world), bool(z_depth),
+                   bool(depth_image))
+        ctx.dev = dev
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        normals, depths, alphas, camtoworlds, Ks = ctx.saved_tensors
+        C, H, W, ps, nl, dl, world, z_depth, depth_image = ctx.cfg
+        dev = ctx.dev
+        # the upstream scalar is read on the device (the trainer's ONE_GRAD
+        # seed as is: no scaling launch either way)
+        if g_loss.dtype != torch.float32 or not g_loss.is_contiguous():
+            g_loss = g_loss.float().contiguous()
+        v_normals = v_depths = v_distort = None
+        d_ptr = vd_ptr = 0
+        vps = 1
+        if nl != 0.0:
+            v_normals = torch.empty((C, H, W, 3), device=dev)
+            if depth_image:
+                v_depths = torch.empty_like(depths)
+                vps = ps
+                d_ptr = depths.data_ptr() + 4 * (ps - 1)
+                vd_ptr = v_depths.data_ptr() + 4 * (ps - 1)
+            else:
+                v_depths = torch.empty((C, H, W, 1), device=dev)
+                d_ptr, vd_ptr = depths.data_ptr(), v_depths.data_ptr()
+        if dl != 0.0:
+            v_distort = torch.empty((C, H, W, 1), device=dev)
+        _lib.call("gsplat_hip_geom_loss_2dgs_bwd", C, H, W, _ptr(normals), d_ptr, ps,
+                  _ptr(alphas), _ptr(camtoworlds), _ptr(Ks), int(z_depth), int(world),
+                  ctypes.c_float(nl), ctypes.c_float(dl), _ptr(g_loss), _ptr(v_normals), vd_ptr,
+                  vps, int(depth_image), _ptr(v_distort), _stream())
+        need = ctx.needs_input_grad
+        return (v_normals if need[0] else None, v_depths if need[1] else None, None, None, None,
+                v_distort if need[5] else None, None, None, None, None, None)
+
+
+def geometry_loss_2dgs(render_normals, depths, alphas, camtoworlds, Ks, render_distort=None,
+                       normal_lambda=5e-2, dist_lambda=1e-2, normals_space="camera",
+                       z_depth=True, _depth_image=False):
+    """The 2DGS trainer's geometry terms (simple_trainer_2dgs.py:611-632),
+    fused in HIP (csrc/geom_loss.hip):
+
+        normal_lambda * mean(1 - <R n, alphas * n_d>) + dist_lambda * mean(render_distort)
+
+    with R = camtoworlds[:, :3, :3], n = render_normals [C,H,W,3] in camera
+    space (normals_space="camera", the rasterizer's image) or already rotated
+    (normals_space="world", rasterization_2dgs's public output: R is skipped),
+    and n_d = depth_to_normal(depths, camtoworlds, Ks, z_depth) formed in the
+    kernel.  depths / alphas / render_distort are [C,H,W,1]; depths may be the
+    last-channel view of an RGB+D render (read in place).  Both means run
+    over all pixels.  Returns a 0-d tensor; gradients go to render_normals,
+    depths and render_distort, alphas is a constant (None), and camtoworlds
+    / Ks requiring a gradient raise NotImplementedError.  A term whose lambda
+    is 0 is skipped and its images may be None.  GPU tensors only.
+    `_depth_image` (internal, the training step): depths is the whole
+    contiguous [C,H,W,D] render, its depth the last channel, and its gradient
+    comes back image-shaped with the other channels zero."""
+    if normals_space not in ("camera", "world"):
+        raise ValueError(f"normals_space: 'camera' or 'world', got {normals_space!r}")
+    nl, dl = float(normal_lambda), float(dist_lambda)
+    if nl != 0.0 and (render_normals is None or depths is None or alphas is None):
+        raise ValueError("geometry_loss_2dgs: the normal term needs render_normals, depths, alphas")
+    if dl != 0.0 and render_distort is None:
+        raise ValueError("geometry_loss_2dgs: the distortion term needs render_distort")
+    if nl == 0.0 and dl == 0.0:
+        raise ValueError("geometry_loss_2dgs: both lambdas are 0")
+    for name, t in (("camtoworlds", camtoworlds), ("Ks", Ks)):
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(
+                f"geometry_loss_2dgs: no gradient of {name} (pose / intrinsics optimisation)")
+    return _GeometryLoss2DGS.apply(render_normals, depths, alphas, camtoworlds, Ks,
+                                   render_distort, nl, dl, normals_space == "world",
+                                   bool(z_depth), bool(_depth_image))
 
 
 def adam_factors(lrs, betas, step):

@@ -517,6 +517,7 @@ def rasterization_2dgs(
     _isect_report=None,
     _camtoworlds: Optional[Tensor] = None,
     _colors_only: bool = False,
+    _geometry: bool = False,
 ):
     """Rasterize N surfels (2DGS) to C images (gsplat/rendering.py:1018-1339).
 
@@ -529,7 +530,14 @@ def rasterization_2dgs(
     inverse viewmats (torch.linalg.inv reads its error flag on the host);
     `_colors_only` (the training step, whose loss reads the colours alone):
     render_normals and render_normals_from_depth are not formed (None) --
-    the world-space rotation and the depth-to-normal pass are skipped."""
+    the world-space rotation and the depth-to-normal pass are skipped;
+    `_geometry` (the training step with its normal-consistency / distortion
+    terms active, losses.geometry_loss_2dgs): the general rasterizer runs and
+    render_normals comes back in CAMERA space (no rotation launch: the loss
+    kernel rotates in registers), render_normals_from_depth is None (the loss
+    kernel forms it), render_colors is the RGB+D render, meta["camtoworlds"]
+    the matrices the loss needs; the densification input is not zero-filled
+    and no 64-bit isect ids are written, as under `_colors_only`."""
     from ._wrapper_2dgs import _SUPPORTED_D as _SUPPORTED_D_2DGS
     from ._wrapper_2dgs import fully_fused_projection_2dgs, rasterize_to_pixels_2dgs
 
@@ -546,6 +554,12 @@ def rasterization_2dgs(
         assert render_mode in ["D", "ED", "RGB+D", "RGB+ED"], (
             "distloss requires depth rendering, render_mode should be D, ED, RGB+D, RGB+ED, "
             f"but got {render_mode}")
+    if _geometry:
+        assert not _colors_only and render_mode == "RGB+D" and depth_mode == "expected", \
+            "_geometry: an RGB+D render with the expected depth"
+    # the training step's renders: the densification input is only a gradient
+    # sink and the isect ids are not read
+    train_step = _colors_only or _geometry
     sh_rest = None
     if isinstance(colors, (tuple, list)):
         # extension (as rasterization()): SH coefficients as the trainer holds
@@ -584,7 +598,7 @@ def rasterization_2dgs(
         camera_ids, gaussian_ids = None, None
     # the densification input only receives a gradient (its values are never
     # read): the training step's (_colors_only) skips the reference's zero fill
-    densify = (torch.empty_like(means2d, dtype=means.dtype) if _colors_only else
+    densify = (torch.empty_like(means2d, dtype=means.dtype) if train_step else
                torch.zeros_like(means2d, dtype=means.dtype)).requires_grad_(True)
 
     tile_width = math.ceil(width / float(tile_size))
@@ -639,9 +653,11 @@ def rasterization_2dgs(
         # only: no 64-bit isect ids (8 of 12 bytes per isect not written)
         # ... and, in the colours-only training step, large surfels' isects
         # only in the tiles their image can reach (the rasterizer culls the
-        # others on every strip: same render, shorter isect list; ABI 34)
+        # others on every strip: same render, shorter isect list; ABI 34).
+        # Not under _geometry: the culling is proven for the colours only,
+        # the normal and distortion images have no unculled comparison yet
         tiles_per_gauss, isect_ids, flatten_ids, counts = pending_isects.finish_capped(
-            _isect_capacity, _isect_status, _isect_report, ids=not _colors_only, ranks=False,
+            _isect_capacity, _isect_status, _isect_report, ids=not train_step, ranks=False,
             surfel_cull=(ray_transforms, opacities) if (_colors_only and TILE_CULL) else None)
     else:
         tiles_per_gauss, isect_ids, flatten_ids = pending_isects.finish(sort=True, ranks=False)
@@ -656,7 +672,7 @@ def rasterization_2dgs(
                                  distloss=distloss, _n_isects_device=counts,
                                  _visible=tiles_per_gauss, _colors_only=_colors_only,
                                  _depths=depth_channel)
-    if _colors_only:
+    if train_step:
         meta = {"camera_ids": camera_ids, "gaussian_ids": gaussian_ids, "radii": radii,
                 "means2d": means2d, "depths": depths, "ray_transforms": ray_transforms,
                 "opacities": opacities, "normals": normals, "tile_width": tile_width,
@@ -667,6 +683,11 @@ def rasterization_2dgs(
                 "gradient_2dgs": densify}
         if counts is not None:
             meta["isect_counts"] = counts
+        if _geometry:
+            meta["camtoworlds"] = torch.linalg.inv(viewmats) if _camtoworlds is None \
+                else _camtoworlds
+            return (render_colors, render_alphas, render_normals, None, render_distort,
+                    render_median, meta)
         return render_colors, render_alphas, None, None, render_distort, render_median, meta
     camtoworlds = torch.linalg.inv(viewmats) if _camtoworlds is None else _camtoworlds
     render_normals_from_depth = None

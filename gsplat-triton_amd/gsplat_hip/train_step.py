@@ -9,9 +9,13 @@ config (sh_degree 3, packed=False, classic rasterize mode, batch 1):
 
 model="2dgs" runs examples/simple_trainer_2dgs.py's default step instead:
 rasterization_2dgs(render_mode="RGB+D") (simple_trainer_2dgs.py:549-563), the
-same loss on the RGB channels (:590-594; normal/distortion losses are off by
-default, :149-160), and the strategy statistics from meta["gradient_2dgs"]
-(key_for_gradient, :307-311).
+same loss on the RGB channels (:590-594), and the strategy statistics from
+meta["gradient_2dgs"] (key_for_gradient, :307-311).  `normal_loss` /
+`dist_loss` (off by default, :149-160) add the normal-consistency and depth
+distortion terms (:611-632) from their start iterations on: the step then
+renders the normal and distortion images with the general surfel rasterizer
+and adds losses.geometry_loss_2dgs (one fused HIP launch pair); before, it
+is the colours-only step unchanged (the reference multiplies the terms by 0).
 
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
 DefaultStrategy schedule after the optimizer step (simple_trainer.py:808-826
@@ -183,9 +187,25 @@ class Trainer:
                  scale_reg: float = 0.0, dp_emulate_world: Optional[int] = None,
                  graph: bool = False, isect_capacity: Optional[int] = None,
                  gaussian_shard: bool = False, visible_adam: bool = False,
-                 packed: bool = False, sparse_grad: bool = False, antialiased: bool = False):
+                 packed: bool = False, sparse_grad: bool = False, antialiased: bool = False,
+                 normal_loss: bool = False, normal_lambda: float = 5e-2,
+                 normal_start_iter: int = 7000, dist_loss: bool = False,
+                 dist_lambda: float = 1e-2, dist_start_iter: int = 3000):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # simple_trainer_2dgs.py:149-160, 611-632: the normal-consistency and
+        # depth-distortion terms, each from its start iteration on (step >
+        # start_iter); the one-GPU 2DGS trainer only
+        self.normal_loss, self.dist_loss = bool(normal_loss), bool(dist_loss)
+        self.normal_lambda, self.dist_lambda = float(normal_lambda), float(dist_lambda)
+        self.normal_start_iter, self.dist_start_iter = int(normal_start_iter), int(dist_start_iter)
+        if self.normal_loss or self.dist_loss:
+            if packed or sparse_grad or gaussian_shard or sharded_optimizer or world_size != 1:
+                raise NotImplementedError(
+                    "normal_loss / dist_loss: the one-GPU dense 2DGS trainer only (not packed, "
+                    "Gaussian-sharded, sharded-optimizer or multi-rank trainers)")
+            if model != "2dgs":
+                raise ValueError("normal_loss / dist_loss are 2DGS terms: model='2dgs'")
         self.model = model
         g = torch.Generator().manual_seed(seed)  # identical on every rank (replicas)
         N = points.shape[0]
@@ -489,10 +509,41 @@ class Trainer:
             cache[key] = (self.viewmats.index_select(0, idx), self.Ks.index_select(0, idx))
         return cache[key]
 
+    def geometry_terms_at(self, it: int):
+        """(normal_lambda, dist_lambda) of step `it`, 0.0 for a term that is
+        off or not yet started (simple_trainer_2dgs.py:612,627: step > start)."""
+        nl = self.normal_lambda if (getattr(self, "normal_loss", False)
+                                    and it > self.normal_start_iter) else 0.0
+        dl = self.dist_lambda if (getattr(self, "dist_loss", False)
+                                  and it > self.dist_start_iter) else 0.0
+        return nl, dl
+
+    def camtoworld(self, ci: int) -> torch.Tensor:
+        """[1,4,4] inverse of camera `ci`'s viewmat, inverted on the host in
+        float64 (the captured step's input block holds the same values)."""
+        cache = self.__dict__.setdefault("_c2w_cache", {})
+        if ci not in cache:
+            vm = self.viewmats[ci].detach().float().cpu().numpy().astype(np.float64)
+            cache[ci] = torch.from_numpy(np.linalg.inv(vm).astype(np.float32))[None].to(
+                self.viewmats.device)
+        return cache[ci]
+
+    def geometry_loss(self, meta, Ks, terms):
+        """The active geometry terms of a render made with `geometry=terms`."""
+        from .losses import geometry_loss_2dgs
+        nl, dl = terms
+        normals, alphas, distort = meta["_geometry"]
+        return geometry_loss_2dgs(normals if nl else None, meta["_rgbd"], alphas,
+                                  meta["camtoworlds"], Ks, distort if dl else None,
+                                  normal_lambda=nl, dist_lambda=dl, _depth_image=True)
+
     def render(self, ci: int, sh_degree: Optional[int] = None,
-               fusion: Optional[_wrapper.StepFusion] = None, world_ci=None):
+               fusion: Optional[_wrapper.StepFusion] = None, world_ci=None, geometry=None):
         """Render camera `ci`; `fusion` (a training step's StepFusion) goes to
         the nodes whose backward hands their gradients to the optimizer.
+        `geometry` (2DGS): the step's (normal_lambda, dist_lambda); with one
+        non-zero the normal and distortion images are rendered too
+        (meta["_geometry"], geometry_loss).
         Gaussian-sharded: a collective -- every rank renders its own camera
         with all ranks' Gaussians (`world_ci`: see world_cameras)."""
         p = self.params
@@ -515,6 +566,16 @@ class Trainer:
         if self.model == "2dgs":
             if hook is not None:
                 hook()
+            if geometry is not None and any(geometry):
+                rc, ra, rn, _, rd, _, meta = rasterization_2dgs(
+                    p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]),
+                    self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1], self.width, self.height,
+                    sh_degree=deg, packed=False, near_plane=0.01, far_plane=1e10,
+                    render_mode="RGB+D", absgrad=absgrad, distloss=bool(geometry[1]),
+                    _fusion=fusion, _camtoworlds=self.camtoworld(ci), _geometry=True)
+                meta["_rgbd"] = rc
+                meta["_geometry"] = (rn, ra, rd)
+                return rc[..., :3], ra, meta
             rc, ra, _, _, _, _, meta = rasterization_2dgs(
                 p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]),
                 self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1], self.width, self.height,
@@ -613,7 +674,8 @@ class Trainer:
             # backward that may run the geometry update (geom_in_proj)
             self._set_means_lr(self.lrs[0] * (0.01 ** (1.0 / self.max_steps)) ** it)
         fusion = self._make_fusion()
-        colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion)
+        terms = self.geometry_terms_at(it)
+        colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion, geometry=terms)
         if self.model == "3dgs":
             # DefaultStrategy.step_pre_backward: the means2d gradient is
             # captured by a hook (retain_grad would clone it into .grad)
@@ -628,6 +690,8 @@ class Trainer:
             ssim_loss = 1.0 - ssim(colors.permute(0, 3, 1, 2), gt.permute(0, 3, 1, 2),
                                    self.window)
             loss = l1 * (1.0 - self.ssim_lambda) + ssim_loss * self.ssim_lambda
+        if any(terms):
+            loss = loss + self.geometry_loss(meta, self.Ks[ci:ci + 1], terms)
         loss = self._regularise(loss)
         if self.fused and loss.dim() == 0:
             # a constant 1.0 seed (no fill launch; the fused loss's backward

@@ -49,7 +49,10 @@ const char *gsplat_hip_last_error(void);
  *     renders); gsplat_hip_watchdog_arm / _beat / _disarm (bounded waits of
  *     a multi-GPU job); gsplat_hip_debug_set_lane_histogram, the
  *     deferred-SH gsplat_hip_adam_step_bounded and the compiled-in variants
- *     measured slower removed. */
+ *     measured slower removed.
+ * 35: gsplat_hip_mcmc_inject_noise.
+ * 36: gsplat_hip_geom_loss_2dgs_fwd / _bwd / _workspace_bytes (the 2DGS
+ *     trainer's normal-consistency and distortion terms). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -970,6 +973,45 @@ int gsplat_hip_depth_to_normal(int C, int H, int W, const float *depths, int64_t
  * for v, out f32[C,HW,3]; one launch.  Forward only. */
 int gsplat_hip_rotate3(int C, int64_t HW, const float *camtoworlds, const float *v, float *out,
                        void *stream);
+
+/* The 2DGS trainer's normal-consistency and distortion terms (ABI 36;
+ * examples/simple_trainer_2dgs.py:611-632 with rasterization_2dgs's rotation
+ * of the normals and its depth_to_normal, gsplat/rendering.py and
+ * gsplat/utils.py:137-224), fused (csrc/geom_loss.hip):
+ *   L = normal_lambda * mean_{c,p}(1 - <R_c n(p), alpha(p) n_d(p)>)
+ *     + dist_lambda * mean_{c,p}(distort(p)),
+ * R_c = camtoworlds[c][:3,:3], n_d the depth_to_normal image of `depths`
+ * (never stored), both means over all C*H*W pixels.  normals[C,H,W,3] are the
+ * rasterizer's camera-space normals, or world-space ones (world_normals = 1:
+ * R is skipped); depths[C,H,W] with depth_stride floats from pixel to pixel
+ * (as gsplat_hip_depth_to_normal); alphas[C,H,W] (a constant), distort[C,H,W].
+ * A term whose lambda is 0 is skipped: its pointers (normal term: normals,
+ * depths, alphas, camtoworlds, Ks, v_normals, v_depths; distortion term:
+ * distort, v_distort) may be NULL and nothing of it is read or written.
+ * fwd: out[0] = L, out[1] = the normal term's mean, out[2] = mean distort
+ *   (device floats), reduced in a fixed order without atomics (bit-identical
+ *   between calls); workspace = gsplat_hip_geom_loss_2dgs_workspace_bytes,
+ *   uninitialised.  Two launches (the reduction and a one-workgroup finish).
+ * bwd: for dL = g_loss[0] (device scalar), one launch, no atomics, every
+ *   element written once: v_normals[C,H,W,3], v_distort[C,H,W], and
+ *   v_depths[C,H,W] with v_depth_stride floats from pixel to pixel;
+ *   zero_rest = 1: v_depths points at the last channel of a
+ *   [C,H,W,v_depth_stride] gradient whose other channels are written as
+ *   zeros (an RGB+D render's gradient). */
+int64_t gsplat_hip_geom_loss_2dgs_workspace_bytes(int C, int H, int W);
+int gsplat_hip_geom_loss_2dgs_fwd(int C, int H, int W, const float *normals, const float *depths,
+                                  int64_t depth_stride, const float *alphas,
+                                  const float *distort, const float *camtoworlds,
+                                  const float *Ks, int z_depth, int world_normals,
+                                  float normal_lambda, float dist_lambda, float *out,
+                                  void *workspace, void *stream);
+int gsplat_hip_geom_loss_2dgs_bwd(int C, int H, int W, const float *normals, const float *depths,
+                                  int64_t depth_stride, const float *alphas,
+                                  const float *camtoworlds, const float *Ks, int z_depth,
+                                  int world_normals, float normal_lambda, float dist_lambda,
+                                  const float *g_loss, float *v_normals, float *v_depths,
+                                  int64_t v_depth_stride, int zero_rest, float *v_distort,
+                                  void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
