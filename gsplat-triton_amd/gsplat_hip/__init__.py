@@ -21,6 +21,7 @@ from ._wrapper_indices import (
     rasterize_to_indices_in_range,
     rasterize_to_indices_in_range_2dgs,
 )
+from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
 from .losses import geometry_loss_2dgs
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
 
@@ -36,6 +37,10 @@ __all__ = [
     "rasterization_2dgs",
     "depth_to_normal",
     "geometry_loss_2dgs",
+    "bilagrid_slice",
+    "bilagrid_tv_loss",
+    "bilagrid_identity",
+    "bilagrid_lr",
     "quat_scale_to_covar_preci",
     "compute_relocation",
     "adam",

@@ -185,6 +185,7 @@ class GraphStep:
     SLOT = 2048  # bytes per input block
     LOSS_RING = 4096  # device slots of the returned per-step losses
     MAX_WORLD = 8  # cameras of a Gaussian-sharded step in the block
+    BIL = 60  # floats [60, 62) of the block: the bilateral grids' Adam factors
 
     def __init__(self, tr, capacity=None, headroom=1.25, lag=2):
         assert graphable(tr), "GraphStep: a fused 3DGS trainer (graph_step.graphable)"
@@ -195,7 +196,8 @@ class GraphStep:
         self.lag = int(lag)  # steps the host may run ahead of its overflow check
         self.capacity = None if capacity is None else int(capacity)
         # device input of the graph: one 2-KB block per step -- f32 [0, 64)
-        # the Adam factors, i64 at byte 256 the rank's camera index, f32
+        # the Adam factors (the bilateral grids' at [BIL, BIL + 2)), i64 at
+        # byte 256 the rank's camera index, f32
         # viewmats [W][16] at byte 512 and Ks [W][9] at
         # byte 1024 (W = the world's cameras: 1, or the Gaussian-sharded job's
         # ranks), the camera-to-world matrix f32 [16] at byte 1536 (2DGS: its
@@ -243,7 +245,11 @@ class GraphStep:
         # active the loss is a sum formed after the photometric launch: the
         # ring is bypassed, as with the regularisers
         self.terms = (0.0, 0.0)
-        self.ring_now = self.ring_loss
+        # the bilateral grid (Trainer(bilateral_grid=True)): the slice between
+        # the render and the loss and 10 x tv added after it (ring bypassed),
+        # the grids' Adam factors at floats [BIL, BIL + 2) of the block
+        self.bil = bool(getattr(tr, "bilateral_grid", False))
+        self.ring_now = self.ring_loss and not self.bil
         self._warmed = set()  # the active-term sets a warm-up step has run for
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # sticky overflow flag
         self.ring_in = _Mapped(self.RING * self.SLOT)
@@ -345,6 +351,10 @@ class GraphStep:
                     _isect_capacity=self.capacity, _isect_status=self.status,
                     _isect_report=(self.ring_out.dev, self.slot), _isect_ids=False, **dkw)
             meta["means2d"].register_hook(lambda g: grad_box.__setitem__("g", g))
+        tv = None
+        if self.bil:  # Trainer._eager_step's slice, the grid chosen on the device
+            from .bilagrid import _slice_tv
+            colors, tv = _slice_tv(tr.bil_grids, colors, self.cam, tr.BIL_TV_WEIGHT)
         vote = None
         if self.vote:  # the ranks' overflow flags, agreed beside the loss kernels
             import torch.distributed as dist
@@ -357,6 +367,8 @@ class GraphStep:
             _channels=3 if tr.model == "2dgs" else None)
         if any(terms):
             loss = loss + tr.geometry_loss(meta, self.K, terms)
+        if tv is not None:
+            loss = loss + tv
         loss = tr._regularise(loss)
         if vote is not None:
             vote.wait()
@@ -393,6 +405,9 @@ class GraphStep:
             if self.dp:
                 tr.opt.capturing = False
         tr.opt.zero_grad(set_to_none=True)
+        if self.bil:
+            tr.bil_opt.step(hyper=self.scal[self.BIL:self.BIL + 2], void=self.status)
+            tr.bil_opt.zero_grad()
         if getattr(tr, "mcmc", False):
             # MCMCStrategy's position noise after the update (Trainer.mcmc_noise):
             # the step and its scale from the block (scale 0 on refine steps,
@@ -446,7 +461,7 @@ class GraphStep:
         if self.dp:
             tr.opt.wait()  # an eager step's deferred all-gathers
         torch.cuda.synchronize(self.dev)
-        self.ring_now = self.ring_loss and not any(self.terms)
+        self.ring_now = self.ring_loss and not any(self.terms) and not self.bil
         try:
             # warm-up on a side stream (torch's capture recipe) as a VOID
             # step: the flag makes every state update a no-op.  Only before
@@ -535,6 +550,11 @@ class GraphStep:
             (s0, ib), (sr, _) = adam_factors([lrs[names.index("sh0")], lrs[names.index("shN")]],
                                              o.betas, step)
             f[sh_off:sh_off + 3] = (s0, sr, ib)
+        if self.bil:  # the grids' Adam: its own betas, the chained schedule's lr
+            from .bilagrid import bilagrid_lr
+            bo = tr.bil_opt
+            bo.lrs[0] = bilagrid_lr(it, tr.max_steps, tr.bil_lr)
+            f[self.BIL], f[self.BIL + 1] = adam_factors(bo.lrs, bo.betas, bo.step_count + 1)[0]
         ci = tr.camera_index(it)
         n = len(self._vm_host)
         world_ci = [(ci - tr.rank + r) % n for r in range(self.W)] if self.gshard else [ci]
@@ -554,11 +574,12 @@ class GraphStep:
     def _key_of(self, deg, stats, terms=None):
         """What a capture is valid for: SH degree, the parameter tensors
         (their generation: a refine replaces them), whether the step
-        accumulates the strategy statistics, and the active geometry terms
-        (2DGS normal / distortion lambdas; None: the current capture's)."""
+        accumulates the strategy statistics, the active geometry terms
+        (2DGS normal / distortion lambdas; None: the current capture's) and
+        whether the bilateral grid is sliced."""
         tr = self.tr
         return (deg, tr.params["means"].shape[0], getattr(tr, "_param_gen", 0), stats,
-                self.terms if terms is None else tuple(terms))
+                self.terms if terms is None else tuple(terms), self.bil)
 
     def _stats_at(self, it):
         st = self.tr.strategy
@@ -612,6 +633,8 @@ class GraphStep:
         self._fill(it, slot)
         self.graph.replay()
         self.tr.opt.step_count += 1
+        if self.bil:
+            self.tr.bil_opt.step_count += 1
         if self.ring_now:
             ret = self.loss_ring[k % self.LOSS_RING]
         elif ret is None:
@@ -658,6 +681,8 @@ class GraphStep:
             self.max_isects = max(self.max_isects, int(self._out[slot][3]))
         self.pending.clear()
         tr.opt.step_count -= len(redo)  # their Adam steps did not happen
+        if self.bil:
+            tr.bil_opt.step_count -= len(redo)
         # (a rank voided by another's overflow keeps at least its capacity)
         self.capacity = max(self.capacity or 0,
                             int(math.ceil(self.max_isects * self.headroom)) + 1)

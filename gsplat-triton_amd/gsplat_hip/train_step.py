@@ -17,6 +17,12 @@ renders the normal and distortion images with the general surfel rasterizer
 and adds losses.geometry_loss_2dgs (one fused HIP launch pair); before, it
 is the colours-only step unchanged (the reference multiplies the terms by 0).
 
+`bilateral_grid=True` (3DGS, simple_trainer.py `use_bilateral_grid`): the
+render goes through the camera's bilateral grid before the loss
+(bilagrid.bilagrid_slice) and 10 x the grids' total variation is added; the
+grids `bil_grids` [cameras, 12, L, Hg, Wg] have their own FusedAdam, stepped
+densely every step.  evaluate() renders without the grid.
+
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
 DefaultStrategy schedule after the optimizer step (simple_trainer.py:808-826
 -> gsplat/strategy/default.py:164-211): refine (grow + prune, one HIP
@@ -174,6 +180,8 @@ def _mean(x: torch.Tensor) -> torch.Tensor:
 class Trainer:
     """Holds the Gaussian parameters, Adam state and strategy statistics."""
 
+    BIL_TV_WEIGHT = 10.0  # simple_trainer.py:664: loss += 10 * tv
+
     LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2,
            "sh0": 2.5e-3, "shN": 2.5e-3 / 20}
 
@@ -190,9 +198,25 @@ class Trainer:
                  packed: bool = False, sparse_grad: bool = False, antialiased: bool = False,
                  normal_loss: bool = False, normal_lambda: float = 5e-2,
                  normal_start_iter: int = 7000, dist_loss: bool = False,
-                 dist_lambda: float = 1e-2, dist_start_iter: int = 3000):
+                 dist_lambda: float = 1e-2, dist_start_iter: int = 3000,
+                 bilateral_grid: bool = False, bilateral_grid_shape=(16, 16, 8)):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # simple_trainer.py use_bilateral_grid / bilateral_grid_shape: one grid
+        # of affine colour transforms per training image, sliced between the
+        # render and the loss (bilagrid.py); the one-GPU dense 3DGS trainer only
+        self.bilateral_grid = bool(bilateral_grid)
+        self.bilateral_grid_shape = tuple(int(v) for v in bilateral_grid_shape)
+        if self.bilateral_grid:
+            if (model != "3dgs" or packed or sparse_grad or visible_adam or gaussian_shard
+                    or sharded_optimizer or world_size != 1):
+                raise NotImplementedError(
+                    "bilateral_grid: the one-GPU dense 3DGS trainer only (not model='2dgs', "
+                    "packed, sparse_grad, visible_adam, Gaussian-sharded, sharded-optimizer or "
+                    "multi-rank trainers)")
+            if len(self.bilateral_grid_shape) != 3 or min(self.bilateral_grid_shape) < 2:
+                raise ValueError("bilateral_grid_shape: (X, Y, W), each >= 2, got "
+                                 f"{bilateral_grid_shape!r}")
         # simple_trainer_2dgs.py:149-160, 611-632: the normal-consistency and
         # depth-distortion terms, each from its start iteration on (step >
         # start_iter); the one-GPU 2DGS trainer only
@@ -337,6 +361,17 @@ class Trainer:
         self._sh_ready = 0
         self.opt = self._make_optimizer(list(self.params.values()))
         self._register_hooks()
+        if self.bilateral_grid:
+            # simple_trainer.py:300-318: Adam(lr 2e-3 sqrt(BS), eps 1e-15) on the
+            # grids, stepped densely over all images every step, its lr on the
+            # chained warm-up / decay schedule (bilagrid_lr)
+            from .bilagrid import bilagrid_identity
+            self.bil_grids = torch.nn.Parameter(
+                bilagrid_identity(len(viewmats), self.bilateral_grid_shape, device=device))
+            self.bil_lr = 2e-3 * math.sqrt(BS)
+            self.bil_opt = FusedAdam([self.bil_grids], [self.bil_lr], betas=(0.9, 0.999),
+                                     eps=1e-15)
+            self._bil_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
         self.viewmats = viewmats.to(device)
         self.Ks = Ks.to(device)
         if targets is None:
@@ -419,7 +454,14 @@ class Trainer:
 
     def moments(self):
         """name -> [exp_avg, exp_avg_sq] as full tensors shaped like the
-        parameter (gathered over the ranks for the sharded optimizer)."""
+        parameter (gathered over the ranks for the sharded optimizer); with
+        the bilateral grid, "bil_grids" holds the grid optimizer's."""
+        out = self._gaussian_moments()
+        if getattr(self, "bilateral_grid", False):
+            out["bil_grids"] = [self.bil_opt.exp_avg[0], self.bil_opt.exp_avg_sq[0]]
+        return out
+
+    def _gaussian_moments(self):
         names = list(self.params)
         if self.sharded:
             return {k: list(mv) for k, mv in zip(names, self.opt.full_state())}
@@ -439,6 +481,10 @@ class Trainer:
     def _load_moments(self, moments):
         params = list(self.params.values())
         names = list(self.params)
+        if "bil_grids" in moments and getattr(self, "bilateral_grid", False):
+            self.bil_opt.params = [self.bil_grids]
+            self.bil_opt.exp_avg = [moments["bil_grids"][0]]
+            self.bil_opt.exp_avg_sq = [moments["bil_grids"][1]]
         if self.sharded:
             step = self.opt.step_count
             self.opt = self._make_optimizer(params)
@@ -681,6 +727,14 @@ class Trainer:
             # captured by a hook (retain_grad would clone it into .grad)
             meta["means2d"].register_hook(lambda g: meta.__setitem__("means2d_grad", g))
         gt = self.targets[ci:ci + 1]
+        tv = None
+        if getattr(self, "bilateral_grid", False):
+            # simple_trainer.py:620-630, 663-665: the camera's grid applied to
+            # the render, 10 x the grids' total variation added to the loss
+            from .bilagrid import _slice_tv, bilagrid_lr
+            self.bil_opt.lrs[0] = bilagrid_lr(it, self.max_steps, self.bil_lr)
+            colors, tv = _slice_tv(self.bil_grids, colors, self._bil_index[ci:ci + 1],
+                                   self.BIL_TV_WEIGHT)
         if self.fused and "_rgbd" in meta:  # 2DGS: the RGB+D render in place
             loss = l1_ssim_loss(meta["_rgbd"], gt, self.ssim_lambda, _channels=3)
         elif self.fused:
@@ -692,6 +746,8 @@ class Trainer:
             loss = l1 * (1.0 - self.ssim_lambda) + ssim_loss * self.ssim_lambda
         if any(terms):
             loss = loss + self.geometry_loss(meta, self.Ks[ci:ci + 1], terms)
+        if tv is not None:
+            loss = loss + tv
         loss = self._regularise(loss)
         if self.fused and loss.dim() == 0:
             # a constant 1.0 seed (no fill launch; the fused loss's backward
@@ -734,6 +790,9 @@ class Trainer:
         else:
             self.opt.step(skip=self._sh_skip(fusion), xform=self._geom_xform(fusion))
         self.opt.zero_grad(set_to_none=True)
+        if tv is not None:
+            self.bil_opt.step()
+            self.bil_opt.zero_grad()
         self.last_meta = meta
         return loss
 
@@ -904,7 +963,7 @@ class Trainer:
                 w.wait()
         params = {k: p.data for k, p in self.params.items()}
         radii2d = self.radii2d if it < self.strategy.refine_scale2d_stop_iter else None
-        new_p, new_m, counts = densify.refine(params, self.moments(), self.grad2d, self.count,
+        new_p, new_m, counts = densify.refine(params, self._gaussian_moments(), self.grad2d, self.count,
                                               it, self.strategy, self.scene_scale,
                                               generator=self.rng, radii2d=radii2d)
         self.params = {k: torch.nn.Parameter(v) for k, v in new_p.items()}
@@ -960,7 +1019,7 @@ class Trainer:
         if self._binoms is None:
             self._binoms = _mcmc.binoms(self.device)
         params = {k: p.data for k, p in self.params.items()}
-        moms = self.moments()
+        moms = self._gaussian_moments()
         dead = torch.sigmoid(params["opacities"].flatten()) <= cfg.min_opacity
         n_reloc = _mcmc.relocate(params, moms, dead, self._binoms, cfg.min_opacity,
                                  generator=self.rng)
@@ -993,7 +1052,7 @@ class Trainer:
             self.params["opacities"].data.clamp_(max=lim)
             self.opt.zero_moments(list(self.params).index("opacities"))
         else:
-            moms = self.moments()
+            moms = self._gaussian_moments()
             densify.reset_opacity({"opacities": self.params["opacities"].data},
                                   {"opacities": moms["opacities"]}, value)
 

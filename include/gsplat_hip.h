@@ -52,7 +52,10 @@ const char *gsplat_hip_last_error(void);
  *     measured slower removed.
  * 35: gsplat_hip_mcmc_inject_noise.
  * 36: gsplat_hip_geom_loss_2dgs_fwd / _bwd / _workspace_bytes (the 2DGS
- *     trainer's normal-consistency and distortion terms). */
+ *     trainer's normal-consistency and distortion terms).
+ * 37: gsplat_hip_bilagrid_slice_fwd / _bwd / _workspace_bytes and
+ *     gsplat_hip_bilagrid_tv_fwd / _bwd / _workspace_bytes (the 3DGS trainer's
+ *     bilateral-grid colour correction). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1012,6 +1015,50 @@ int gsplat_hip_geom_loss_2dgs_bwd(int C, int H, int W, const float *normals, con
                                   const float *g_loss, float *v_normals, float *v_depths,
                                   int64_t v_depth_stride, int zero_rest, float *v_distort,
                                   void *stream);
+
+/* Bilateral-grid colour correction (ABI 37; examples/lib_bilagrid.py
+ * BilateralGrid / slice / total_variation_loss, fused in csrc/bilagrid.hip).
+ * grids[N,12,L,Hg,Wg] float32: per training image a 3-D grid of 3x4 affine
+ * colour transforms, channel c = 4 i + j element (i, j); L, Hg, Wg >= 2.
+ * grid_index[B] (device int64) names the grid of each image of rgb[B,H,W,3];
+ * it is read on the device (values outside [0, N) are clamped).
+ * slice, for pixel (x, y):
+ *   fx = (x + 0.5) / W * (Wg - 1), fy = (y + 0.5) / H * (Hg - 1),
+ *   gray = 0.299 r + 0.587 g + 0.114 b, fz = clamp(gray, 0, 1) * (L - 1),
+ *   A = trilinear interpolation of the grid at (fz, fy, fx),
+ *   out_i = A[4i] r + A[4i+1] g + A[4i+2] b + A[4i+3]
+ * (grid_sample, bilinear, align_corners, border padding, then the matmul).
+ * fwd: one launch, out[B,H,W,3].
+ * bwd: three launches, no atomics.  v_rgb[B,H,W,3] is written once per
+ *   pixel; the gradient through the guidance is zero where gray <= 0 or
+ *   gray >= 1 (torch's clamp).  The grid gradient is ADDED to
+ *   v_grids[N,12,L,Hg,Wg], which the caller initialises
+ *   (gsplat_hip_bilagrid_tv_bwd writes every element, or zeros): a workgroup
+ *   sums the pixels of one cell chunk in registers and stores one partial
+ *   slab into the workspace (gsplat_hip_bilagrid_slice_workspace_bytes,
+ *   uninitialised, 16-B aligned), and a finish kernel adds the slabs of a
+ *   node in a fixed order, one thread per element: bit-identical between
+ *   calls.  Rows of grids that no image indexes are not touched.
+ * tv = (1/N) sum over the axes d of L, Hg, Wg of
+ *   sum (x[i+1] - x[i])^2 / (12 * elements of the difference along d of one
+ *   grid).  fwd: out[0] = scale * tv, out[1] = tv (device floats), reduced in
+ *   a fixed order without atomics (bit-identical between calls); workspace =
+ *   gsplat_hip_bilagrid_tv_workspace_bytes, uninitialised; two launches.
+ *   bwd: v_grids = g_loss[0] * scale * dtv/dgrids (g_loss a device scalar),
+ *   every element written exactly once, one launch. */
+int64_t gsplat_hip_bilagrid_slice_workspace_bytes(int B, int H, int W, int L, int Hg, int Wg);
+int gsplat_hip_bilagrid_slice_fwd(int B, int H, int W, int N, int L, int Hg, int Wg,
+                                  const float *grids, const int64_t *grid_index,
+                                  const float *rgb, float *out, void *stream);
+int gsplat_hip_bilagrid_slice_bwd(int B, int H, int W, int N, int L, int Hg, int Wg,
+                                  const float *grids, const int64_t *grid_index,
+                                  const float *rgb, const float *v_out, float *v_rgb,
+                                  float *v_grids, void *workspace, void *stream);
+int64_t gsplat_hip_bilagrid_tv_workspace_bytes(int N, int L, int Hg, int Wg);
+int gsplat_hip_bilagrid_tv_fwd(int N, int L, int Hg, int Wg, const float *grids, float scale,
+                               float *out, void *workspace, void *stream);
+int gsplat_hip_bilagrid_tv_bwd(int N, int L, int Hg, int Wg, const float *grids, float scale,
+                               const float *g_loss, float *v_grids, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
