@@ -11,6 +11,7 @@
 // caller holds them ([N,3] means, [N,4] quats, [N,3] scales).
 #include "common.h"
 #include "geom_adam.h"
+#include "wave_ops.h"
 #include "../../include/gsplat_hip.h"
 
 namespace gs {
@@ -227,7 +228,71 @@ struct ProjBwdArgs {
   int64_t nnz;
   int sparse;
   GeomAdam ga;  // projection_bwd_kernel<true>: the geometry Adam instead of the stores
+  float *pose_ws;  // projection_bwd_kernel<true, true>: [gridDim.x][16] per-block pose partials
 };
+
+// The view-matrix partials vR | vt of one visible (camera, Gaussian) pair,
+// derived again from the kernel's inputs (no compensations): the pose variant
+// of the fused backward calls this AFTER its gradients are formed, with an
+// index, predicate and camera the compiler cannot relate to the first
+// derivation's.  Formed inside that derivation instead (as v_viewmats is), or
+// sharing its camera-only subexpressions, the extra consumers change how the
+// compiler pairs and contracts its multiply-adds, and the geometry update is
+// no longer gsplat_hip_projection_bwd_adam's bit for bit (measured).
+GS_INLINE void pose_partials(const ProjBwdArgs &a, const Cam &k, int W, int H, size_t idx,
+                             size_t n, float (&vR)[3][3], float (&vt)[3]) {
+  const float *cn = a.conics + 3 * idx;
+  const float ca = cn[0], cb = cn[1], cc = cn[2];
+  const float *vc = a.v_conics + 3 * idx;
+  const float va = vc[0], vb = 0.5f * vc[1], vcc = vc[2];
+  const float dxx = -(ca * va * ca + cb * vcc * cb + 2.f * cb * vb * ca);
+  const float dxy = -(ca * vb * cc + cb * vb * cb + cb * vcc * cc + ca * va * cb);
+  const float dyy = -(cb * va * cb + cc * vcc * cc + 2.f * cc * vb * cb);
+  const float4 q = *reinterpret_cast<const float4 *>(a.quats + 4 * n);
+  const float *sp = a.scales + 3 * n;
+  const float *mp = a.means + 3 * n;
+  const float m[3] = {mp[0], mp[1], mp[2]};
+  const M3 C3 = covar_world(quat_to_rotmat(q.x, q.y, q.z, q.w), sp[0], sp[1], sp[2]);
+  float mc[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    mc[i] = k.R.m[i][0] * m[0] + k.R.m[i][1] * m[1] + k.R.m[i][2] * m[2] + k.t[i];
+  const M3 Cc = mul(mul(k.R, C3), transpose(k.R));
+  const ProjOut p = persp(mc[0], mc[1], mc[2], Cc, k, W, H);
+  const float iz = 1.f / mc[2];
+  M3 v3;
+  v3.m[0][0] = p.Jxx * dxx * p.Jxx;
+  v3.m[1][1] = p.Jyy * dyy * p.Jyy;
+  v3.m[2][2] = p.Jxz * dxx * p.Jxz + p.Jyz * dyy * p.Jyz + 2.f * p.Jyz * dxy * p.Jxz;
+  v3.m[0][1] = v3.m[1][0] = p.Jxx * dxy * p.Jyy;
+  v3.m[0][2] = v3.m[2][0] = p.Jxx * dxx * p.Jxz + p.Jxx * dxy * p.Jyz;
+  v3.m[1][2] = v3.m[2][1] = p.Jyy * dxy * p.Jxz + p.Jyy * dyy * p.Jyz;
+  const float vm2x = a.v_means2d[2 * idx], vm2y = a.v_means2d[2 * idx + 1];
+  const float(*cm)[3] = Cc.m;
+  const float Jc_xx = p.Jxx * cm[0][0] + p.Jxz * cm[0][2];
+  const float Jc_xy = p.Jxx * cm[0][1] + p.Jxz * cm[1][2];
+  const float Jc_xz = p.Jxx * cm[0][2] + p.Jxz * cm[2][2];
+  const float Jc_yx = p.Jyy * cm[0][1] + p.Jyz * cm[0][2];
+  const float Jc_yy = p.Jyy * cm[1][1] + p.Jyz * cm[1][2];
+  const float Jc_yz = p.Jyy * cm[1][2] + p.Jyz * cm[2][2];
+  const float vJxx = 2.f * (dxx * Jc_xx + dxy * Jc_yx);
+  const float vJxz = 2.f * (dxx * Jc_xz + dxy * Jc_yz);
+  const float vJyy = 2.f * (dxy * Jc_xy + dyy * Jc_yy);
+  const float vJyz = 2.f * (dxy * Jc_xz + dyy * Jc_yz);
+  const float iz2 = iz * iz;
+  vt[0] = p.Jxx * vm2x + (p.clamp_x ? 0.f : -vJxz * k.fx * iz2);
+  vt[1] = p.Jyy * vm2y + (p.clamp_y ? 0.f : -vJyz * k.fy * iz2);
+  float tmp = vJxx * p.Jxx + vJyy * p.Jyy + 2.f * (vJxz * p.Jxz + vJyz * p.Jyz);
+  tmp -= p.clamp_x ? vJxz * p.Jxz : 0.f;
+  tmp -= p.clamp_y ? vJyz * p.Jyz : 0.f;
+  vt[2] = p.Jxz * vm2x + p.Jyz * vm2y - iz * tmp;
+  if (a.v_depths) vt[2] += a.v_depths[idx];
+  const M3 vRc = mul(mul(v3, k.R), C3);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) vR[i][j] = vt[i] * m[j] + 2.f * vRc.m[i][j];
+}
 
 // FUSE: the geometry-Adam epilogue (struct GeomAdam; C == 1, store mode).
 // Its lane's optimizer rows (33 floats) and gradient inputs are loaded at
@@ -235,7 +300,13 @@ struct ProjBwdArgs {
 // following it group by group (the stores of one group could alias the next
 // group's loads as far as the compiler knows): 93.6 us as an epilogue
 // issuing them after the algebra at M2 (profiles/r5/).
-template <bool FUSE = false>
+// POSE (with FUSE; camera pose refinement, csrc/pose.hip): after the Adam
+// stores the block also sums the 12 view-matrix partials and the visible
+// Gaussians' v_dirs (minus the camera-centre gradient of the SH colours) and
+// stores the 15 sums in row blockIdx.x of pose_ws -- no atomics, no zeroing.
+// The partials come from pose_partials, after the gradients: the code up to
+// there is the plain instantiation's.
+template <bool FUSE = false, bool POSE = false>
 __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
   const bool packed = a.camera_ids != nullptr;
   int c, n;
@@ -398,6 +469,19 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
   asm volatile("" : "+v"(vm[0]), "+v"(vm[1]), "+v"(vm[2]), "+v"(vq[0]), "+v"(vq[1]),
                "+v"(vq[2]), "+v"(vq[3]), "+v"(vs[0]), "+v"(vs[1]), "+v"(vs[2]));
 
+  // POSE: arrays of their own -- vR / vt above keep exactly the consumers
+  // they have in the plain instantiation (the v_viewmats epilogues below)
+  float pR[3][3] = {{0.f}}, pt[3] = {0.f, 0.f, 0.f};
+  if (POSE) {
+    // indices, predicate, camera and image size made opaque: no load, branch
+    // or camera-only subexpression of the second derivation can be merged
+    // with (or hoisted out of) the first one's block
+    size_t idx2 = idx, n2 = (size_t)n;
+    int valid2 = valid, c2 = c, W2 = a.W, H2 = a.H;
+    asm volatile("" : "+v"(idx2), "+v"(n2), "+v"(valid2), "+v"(c2), "+v"(W2), "+v"(H2));
+    if (valid2) pose_partials(a, load_cam(a.viewmats, a.Ks, c2), W2, H2, idx2, n2, pR, pt);
+  }
+
   if (a.sparse) {
     if (valid) {  // COO values, one row per packed entry
       float *o = a.v_means + 3 * idx;
@@ -466,6 +550,29 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
     for (int j = 0; j < 3; ++j) atomic_add_f32(a.v_scales + 3 * (size_t)n + j, vs[j]);
   }
 
+  if (POSE) {
+    // one reduce-scatter of the 15 fields per wave (lane l then holds the
+    // wave's total of field rs_field(l)), the four waves added in order
+    __shared__ float pred[4][16];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    float v[15];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) v[i * 4 + j] = pR[i][j];
+      v[i * 4 + 3] = pt[i];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[12 + j] = valid ? gvd[j] : 0.f;
+    const float z = reduce_scatter<15>(v, lane);
+    if ((lane & 3) == 0) pred[wid][rs_field(lane)] = z;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+      const int e = threadIdx.x;
+      const float s = ((pred[0][e] + pred[1][e]) + pred[2][e]) + pred[3][e];
+      a.pose_ws[(size_t)blockIdx.x * 16 + e] = e < 15 ? s : 0.f;
+    }
+  }
   if (a.v_viewmats && packed) {
     // entries are camera-major: a wave spans one camera except at camera
     // boundaries, where its lanes add their partials one by one
@@ -579,14 +686,14 @@ extern "C" int gsplat_hip_projection_bwd(
 // [means, log_scales, quats, logits]; lrs[4] with the 1-based step, or
 // hyper_device f32[8] = (lr_i / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) per
 // group in that order (then lrs / step are unused); skip_device may be NULL.
-extern "C" int gsplat_hip_projection_bwd_adam(
+static int projection_bwd_adam_impl(
     int N, const float *means, const float *quats, const float *scales, const float *viewmats,
     const float *Ks, int width, int height, float eps2d, const int32_t *radii,
     const float *conics, const float *v_means2d, const float *v_depths, const float *v_conics,
     const float *v_dirs, const float *v_opac, const float *opac, float *const *params,
     float *const *exp_avgs, float *const *exp_avg_sqs, const float *lrs, float beta1,
     float beta2, float eps, int step, const float *hyper_device, const int32_t *skip_device,
-    void *stream) {
+    float *pose_ws, void *stream) {
   GS_REQUIRE(N >= 0, "projection_bwd_adam: negative N=%d", N);
   if (N == 0) return 0;
   GS_REQUIRE(params && exp_avgs && exp_avg_sqs, "projection_bwd_adam: null group arrays");
@@ -619,10 +726,49 @@ extern "C" int gsplat_hip_projection_bwd_adam(
                 nullptr, v_means2d, v_depths, v_conics, nullptr, nullptr, nullptr, nullptr,
                 nullptr, 1};
   a.ga = ga;
-  hipLaunchKernelGGL(projection_bwd_kernel<true>, dim3((N + 255) / 256, 1), dim3(256), 0,
-                     (hipStream_t)stream, a);
+  a.pose_ws = pose_ws;
+  if (pose_ws)
+    hipLaunchKernelGGL((projection_bwd_kernel<true, true>), dim3((N + 255) / 256, 1), dim3(256),
+                       0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(projection_bwd_kernel<true>, dim3((N + 255) / 256, 1), dim3(256), 0,
+                       (hipStream_t)stream, a);
   GS_CHECK_LAUNCH("projection_bwd_adam");
   return 0;
+}
+
+extern "C" int gsplat_hip_projection_bwd_adam(
+    int N, const float *means, const float *quats, const float *scales, const float *viewmats,
+    const float *Ks, int width, int height, float eps2d, const int32_t *radii,
+    const float *conics, const float *v_means2d, const float *v_depths, const float *v_conics,
+    const float *v_dirs, const float *v_opac, const float *opac, float *const *params,
+    float *const *exp_avgs, float *const *exp_avg_sqs, const float *lrs, float beta1,
+    float beta2, float eps, int step, const float *hyper_device, const int32_t *skip_device,
+    void *stream) {
+  return projection_bwd_adam_impl(N, means, quats, scales, viewmats, Ks, width, height, eps2d,
+                                  radii, conics, v_means2d, v_depths, v_conics, v_dirs, v_opac,
+                                  opac, params, exp_avgs, exp_avg_sqs, lrs, beta1, beta2, eps,
+                                  step, hyper_device, skip_device, nullptr, stream);
+}
+
+// gsplat_hip_projection_bwd_adam that also leaves the camera pose partials of
+// its blocks in pose_workspace (ABI 38, gsplat_hip_pose_workspace_bytes(N);
+// read by gsplat_hip_pose_bwd_adam): the geometry update is the same code and
+// bit-identical.
+extern "C" int gsplat_hip_projection_bwd_adam_pose(
+    int N, const float *means, const float *quats, const float *scales, const float *viewmats,
+    const float *Ks, int width, int height, float eps2d, const int32_t *radii,
+    const float *conics, const float *v_means2d, const float *v_depths, const float *v_conics,
+    const float *v_dirs, const float *v_opac, const float *opac, float *const *params,
+    float *const *exp_avgs, float *const *exp_avg_sqs, const float *lrs, float beta1,
+    float beta2, float eps, int step, const float *hyper_device, const int32_t *skip_device,
+    void *pose_workspace, void *stream) {
+  GS_REQUIRE(pose_workspace || N == 0, "projection_bwd_adam_pose: null workspace");
+  return projection_bwd_adam_impl(N, means, quats, scales, viewmats, Ks, width, height, eps2d,
+                                  radii, conics, v_means2d, v_depths, v_conics, v_dirs, v_opac,
+                                  opac, params, exp_avgs, exp_avg_sqs, lrs, beta1, beta2, eps,
+                                  step, hyper_device, skip_device,
+                                  reinterpret_cast<float *>(pose_workspace), stream);
 }
 
 namespace gs {

@@ -23,6 +23,7 @@ from ._wrapper_indices import (
 )
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
 from .losses import geometry_loss_2dgs
+from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
 
 __all__ = [
@@ -41,6 +42,7 @@ __all__ = [
     "bilagrid_tv_loss",
     "bilagrid_identity",
     "bilagrid_lr",
+    "pose_adjust",
     "quat_scale_to_covar_preci",
     "compute_relocation",
     "adam",

@@ -12,7 +12,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB", os.path.join(_HERE, "libgsplat_hip.so"))
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int
@@ -177,6 +177,15 @@ _SIGS = {
     "gsplat_hip_bilagrid_tv_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "gsplat_hip_bilagrid_tv_fwd": (_i32, [_i32, _i32, _i32, _i32, _p, _f, _p, _p, _p]),
     "gsplat_hip_bilagrid_tv_bwd": (_i32, [_i32, _i32, _i32, _i32, _p, _f, _p, _p, _p]),
+    "gsplat_hip_pose_workspace_bytes": (_i64, [_i32]),
+    "gsplat_hip_pose_apply": (_i32, [_i32, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_projection_bwd_adam_pose": (_i32, [_i32, _p, _p, _p, _p, _p, _i32, _i32, _f, _p,
+                                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f,
+                                                   _f, _f, _i32, _p, _p, _p, _p]),
+    "gsplat_hip_pose_bwd_adam": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f,
+                                        _f, _i32, _p, _p, _p]),
+    "gsplat_hip_pose_adjust_fwd": (_i32, [_i64, _p, _p, _p, _p]),
+    "gsplat_hip_pose_adjust_bwd": (_i32, [_i64, _p, _p, _p, _p, _p]),
     "gsplat_hip_watchdog_arm": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
     "gsplat_hip_watchdog_beat": (_i32, [ctypes.c_char_p]),
     "gsplat_hip_watchdog_set_fallback": (_i32, [_i32, ctypes.c_char_p, _i32]),

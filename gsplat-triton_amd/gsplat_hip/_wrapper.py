@@ -738,6 +738,9 @@ class GeomAdamInBackward:
             list(exp_avg_sqs)
         self.lrs, self.betas, self.eps, self.step = [float(x) for x in lrs], betas, eps, step
         self.hyper, self.skip = hyper, skip  # captured step: device factors f32[8], void flag
+        # camera pose optimisation: the backward also leaves its blocks' pose
+        # partials here (pose.pose_workspace; gsplat_hip_projection_bwd_adam_pose)
+        self.pose_ws = None
         self.applied = False
 
     def run(self, means, quats, scales, viewmats, Ks, width, height, eps2d, radii, conics,
@@ -748,15 +751,21 @@ class GeomAdamInBackward:
         assert [t.shape[0] for t in self.params] == [N] * 4
         P = ctypes.c_void_p * 4
         v_opac = fusion.v_opac_in
-        _lib.call("gsplat_hip_projection_bwd_adam", N, _ptr(means), _ptr(quats), _ptr(scales),
-                  _ptr(viewmats), _ptr(Ks), int(width), int(height), float(eps2d), _ptr(radii),
-                  _ptr(conics), _ptr(v_means2d), _ptr(v_depths), _ptr(v_conics),
-                  _ptr(fusion.v_dirs), _ptr(v_opac), _ptr(fusion.opac_act),
-                  P(*[t.data_ptr() for t in self.params]),
-                  P(*[t.data_ptr() for t in self.exp_avgs]),
-                  P(*[t.data_ptr() for t in self.exp_avg_sqs]),
-                  (ctypes.c_float * 4)(*self.lrs), float(self.betas[0]), float(self.betas[1]),
-                  float(self.eps), int(self.step), _ptr(self.hyper), _ptr(self.skip), _stream())
+        args = (N, _ptr(means), _ptr(quats), _ptr(scales),
+                _ptr(viewmats), _ptr(Ks), int(width), int(height), float(eps2d), _ptr(radii),
+                _ptr(conics), _ptr(v_means2d), _ptr(v_depths), _ptr(v_conics),
+                _ptr(fusion.v_dirs), _ptr(v_opac), _ptr(fusion.opac_act),
+                P(*[t.data_ptr() for t in self.params]),
+                P(*[t.data_ptr() for t in self.exp_avgs]),
+                P(*[t.data_ptr() for t in self.exp_avg_sqs]),
+                (ctypes.c_float * 4)(*self.lrs), float(self.betas[0]), float(self.betas[1]),
+                float(self.eps), int(self.step), _ptr(self.hyper), _ptr(self.skip))
+        if self.pose_ws is not None:
+            assert self.pose_ws.dtype == torch.float32 and \
+                self.pose_ws.numel() >= 16 * ((N + 255) // 256), (self.pose_ws.shape, N)
+            _lib.call("gsplat_hip_projection_bwd_adam_pose", *args, _ptr(self.pose_ws), _stream())
+        else:
+            _lib.call("gsplat_hip_projection_bwd_adam", *args, _stream())
         self.applied = True
 
 

@@ -186,6 +186,7 @@ class GraphStep:
     LOSS_RING = 4096  # device slots of the returned per-step losses
     MAX_WORLD = 8  # cameras of a Gaussian-sharded step in the block
     BIL = 60  # floats [60, 62) of the block: the bilateral grids' Adam factors
+    POSE = 62  # floats [62, 64): the pose table's Adam factors (Trainer(pose_opt=True))
 
     def __init__(self, tr, capacity=None, headroom=1.25, lag=2):
         assert graphable(tr), "GraphStep: a fused 3DGS trainer (graph_step.graphable)"
@@ -250,6 +251,12 @@ class GraphStep:
         # the grids' Adam factors at floats [BIL, BIL + 2) of the block
         self.bil = bool(getattr(tr, "bilateral_grid", False))
         self.ring_now = self.ring_loss and not self.bil
+        # camera pose optimisation (Trainer(pose_opt=True) / pose_noise): the
+        # step's view matrix made from the block's by pose.pose_apply right
+        # after the fetch, the pose Adam (its factors at floats [POSE, POSE + 2))
+        # a launch after the other updates
+        self.pose = bool(getattr(tr, "pose_opt", False))
+        self.pose_any = bool(getattr(tr, "pose_active", False))
         self._warmed = set()  # the active-term sets a warm-up step has run for
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # sticky overflow flag
         self.ring_in = _Mapped(self.RING * self.SLOT)
@@ -306,11 +313,16 @@ class GraphStep:
             # groups follow when their update is not fused into the SH backward
             assert [names[i] for i in idx][:len(tr.GEOM)] == list(tr.GEOM), (idx, names)
             ga = tr.geom_adam_in_backward(1, hyper=self.scal[:2 * len(idx)], skip=self.status)
+            if self.pose:
+                ga.pose_ws = tr._pose_workspace()
         fusion = _wrapper.StepFusion(sh_adam=fa, geom=tr.geom_fuse, geom_adam=ga) \
             if (fa is not None or tr.geom_fuse) else None
         # the first launch also fetches this step's input block (the ring slot)
         scales, opac = activate(p["scales"], p["opacities"], fusion,
                                 fetch=(self.ring_in.dev, self.SLOT, self.RING, self.seq, self.blk))
+        vm = self.vm
+        if self.pose_any:  # Trainer._eager_step's launch (a), camera and index from the block
+            vm = tr._pose_viewmat(self.vm, self.cam)
         dkw = {}
         if self.gshard:  # the world's cameras from the block, shard sizes fixed per capture
             dkw = dict(distributed=True, _world_cameras=(self.vm_w, self.K_w),
@@ -344,7 +356,7 @@ class GraphStep:
             with _wrapper.fwd_split(getattr(tr, "split_div", None),
                                     getattr(tr, "split_threshold", None)):
                 colors, _, meta = rasterization(
-                    p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), self.vm, self.K,
+                    p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), vm, self.K,
                     tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
                     far_plane=1e10, radius_clip=0.0,
                     rasterize_mode=getattr(tr, "rasterize_mode", "classic"), _fusion=fusion,
@@ -408,6 +420,13 @@ class GraphStep:
         if self.bil:
             tr.bil_opt.step(hyper=self.scal[self.BIL:self.BIL + 2], void=self.status)
             tr.bil_opt.zero_grad()
+        if self.pose:  # Trainer._pose_step, factors and void flag on the device
+            from .pose import pose_bwd_adam
+            assert ga is not None and ga.applied, "pose_opt: the geometry Adam in the backward"
+            pose_bwd_adam(tr._pose_ws, p["means"].shape[0], self.vm, self.cam, tr.pose_embeds,
+                          tr._pose_m, tr._pose_v, 0.0, tr.pose_opt_reg, 1,
+                          noise=tr.pose_noise_table, hyper=self.scal[self.POSE:self.POSE + 2],
+                          skip=self.status)
         if getattr(tr, "mcmc", False):
             # MCMCStrategy's position noise after the update (Trainer.mcmc_noise):
             # the step and its scale from the block (scale 0 on refine steps,
@@ -460,6 +479,8 @@ class GraphStep:
         _wrapper._timers = None  # no timing events inside the graph
         if self.dp:
             tr.opt.wait()  # an eager step's deferred all-gathers
+        if self.pose:
+            tr._pose_workspace()  # sized for the Gaussians, allocated outside the capture
         torch.cuda.synchronize(self.dev)
         self.ring_now = self.ring_loss and not any(self.terms) and not self.bil
         try:
@@ -555,6 +576,10 @@ class GraphStep:
             bo = tr.bil_opt
             bo.lrs[0] = bilagrid_lr(it, tr.max_steps, tr.bil_lr)
             f[self.BIL], f[self.BIL + 1] = adam_factors(bo.lrs, bo.betas, bo.step_count + 1)[0]
+        if self.pose:
+            from .pose import BETAS
+            f[self.POSE], f[self.POSE + 1] = adam_factors([tr.pose_lr_at(it)], BETAS,
+                                                          tr.pose_step_count + 1)[0]
         ci = tr.camera_index(it)
         n = len(self._vm_host)
         world_ci = [(ci - tr.rank + r) % n for r in range(self.W)] if self.gshard else [ci]
@@ -575,11 +600,13 @@ class GraphStep:
         """What a capture is valid for: SH degree, the parameter tensors
         (their generation: a refine replaces them), whether the step
         accumulates the strategy statistics, the active geometry terms
-        (2DGS normal / distortion lambdas; None: the current capture's) and
-        whether the bilateral grid is sliced."""
+        (2DGS normal / distortion lambdas; None: the current capture's),
+        whether the bilateral grid is sliced and whether the camera pose is
+        adjusted / optimised."""
         tr = self.tr
         return (deg, tr.params["means"].shape[0], getattr(tr, "_param_gen", 0), stats,
-                self.terms if terms is None else tuple(terms), self.bil)
+                self.terms if terms is None else tuple(terms), self.bil,
+                (self.pose_any, self.pose))
 
     def _stats_at(self, it):
         st = self.tr.strategy
@@ -635,6 +662,8 @@ class GraphStep:
         self.tr.opt.step_count += 1
         if self.bil:
             self.tr.bil_opt.step_count += 1
+        if self.pose:
+            self.tr.pose_step_count += 1
         if self.ring_now:
             ret = self.loss_ring[k % self.LOSS_RING]
         elif ret is None:
@@ -683,6 +712,8 @@ class GraphStep:
         tr.opt.step_count -= len(redo)  # their Adam steps did not happen
         if self.bil:
             tr.bil_opt.step_count -= len(redo)
+        if self.pose:
+            tr.pose_step_count -= len(redo)
         # (a rank voided by another's overflow keeps at least its capacity)
         self.capacity = max(self.capacity or 0,
                             int(math.ceil(self.max_isects * self.headroom)) + 1)

@@ -23,6 +23,14 @@ render goes through the camera's bilateral grid before the loss
 grids `bil_grids` [cameras, 12, L, Hg, Wg] have their own FusedAdam, stepped
 densely every step.  evaluate() renders without the grid.
 
+`pose_opt=True` (3DGS, simple_trainer.py `pose_opt`): the camera is adjusted
+by its row of `pose_embeds` [cameras, 9] before the render (pose.pose_apply,
+`pose_noise` a fixed perturbation applied first), the projection backward
+that runs the geometry Adam also leaves the pose partials, and
+pose.pose_bwd_adam turns them into the row's gradient and steps the table's
+dense Adam with L2 weight decay -- no view matrix requires grad, the step
+stays fused and graph-replayed.  evaluate() renders the cameras unadjusted.
+
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
 DefaultStrategy schedule after the optimizer step (simple_trainer.py:808-826
 -> gsplat/strategy/default.py:164-211): refine (grow + prune, one HIP
@@ -199,9 +207,36 @@ class Trainer:
                  normal_loss: bool = False, normal_lambda: float = 5e-2,
                  normal_start_iter: int = 7000, dist_loss: bool = False,
                  dist_lambda: float = 1e-2, dist_start_iter: int = 3000,
-                 bilateral_grid: bool = False, bilateral_grid_shape=(16, 16, 8)):
+                 bilateral_grid: bool = False, bilateral_grid_shape=(16, 16, 8),
+                 pose_opt: bool = False, pose_opt_lr: float = 1e-5, pose_opt_reg: float = 1e-6,
+                 pose_noise: float = 0.0):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # simple_trainer.py pose_opt / pose_opt_lr / pose_opt_reg / pose_noise:
+        # a pose row per training image refined by its own Adam (pose.py); the
+        # step stays fused: only where the geometry Adam runs in the
+        # projection backward (that backward forms the pose partials)
+        self.pose_opt, self.pose_noise = bool(pose_opt), float(pose_noise)
+        self.pose_opt_reg = float(pose_opt_reg)
+        if self.pose_noise < 0.0:
+            raise ValueError(f"pose_noise: a standard deviation >= 0, got {pose_noise!r}")
+        if self.pose_opt or self.pose_noise > 0.0:
+            what = "pose_opt" if self.pose_opt else "pose_noise"
+            off = [name for name, on in (
+                ("model='2dgs'", model != "3dgs"), ("packed", packed),
+                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
+                ("antialiased", antialiased), ("opacity_reg", float(opacity_reg) != 0.0),
+                ("scale_reg", float(scale_reg) != 0.0), ("gaussian_shard", gaussian_shard),
+                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
+                ("fused=False", not fused),
+                ("GSPLAT_HIP_GEOM_FUSE=0", os.environ.get("GSPLAT_HIP_GEOM_FUSE", "1") == "0"),
+                ("GSPLAT_HIP_GEOM_IN_PROJ=0",
+                 os.environ.get("GSPLAT_HIP_GEOM_IN_PROJ", "1") == "0")) if on]
+            if off:
+                raise NotImplementedError(
+                    f"{what}: the one-GPU dense fused 3DGS trainer with the geometry Adam in "
+                    f"the projection backward only; not with {', '.join(off)}")
+
         # simple_trainer.py use_bilateral_grid / bilateral_grid_shape: one grid
         # of affine colour transforms per training image, sliced between the
         # render and the loss (bilagrid.py); the one-GPU dense 3DGS trainer only
@@ -372,6 +407,26 @@ class Trainer:
             self.bil_opt = FusedAdam([self.bil_grids], [self.bil_lr], betas=(0.9, 0.999),
                                      eps=1e-15)
             self._bil_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
+        self.pose_lr = float(pose_opt_lr) * math.sqrt(BS)
+        if self.pose_opt or self.pose_noise > 0.0:
+            assert self.geom_in_proj, "pose_opt: the geometry Adam in the projection backward"
+            n_img = len(viewmats)
+            # utils.py CameraOptModule: embeds.weight [n, 9], zero_init; its
+            # Adam(lr pose_opt_lr sqrt(BS), weight_decay pose_opt_reg) state
+            self.pose_embeds = torch.zeros(n_img, 9, device=device)
+            self._pose_m = torch.zeros(n_img, 9, device=device)
+            self._pose_v = torch.zeros(n_img, 9, device=device)
+            self.pose_step_count = 0
+            # pose_perturb.random_init(pose_noise): a fixed table N(0, pose_noise)
+            # from a generator of its own (the Gaussians' draws are a plain trainer's)
+            self.pose_noise_table = None
+            if self.pose_noise > 0.0:
+                gp = torch.Generator().manual_seed(seed + 1013)
+                self.pose_noise_table = (torch.randn(n_img, 9, generator=gp)
+                                         * self.pose_noise).to(device)
+            self._pose_vm = torch.empty(1, 4, 4, device=device)  # the step's view matrix
+            self._pose_index = torch.arange(n_img, dtype=torch.int64, device=device)
+            self._pose_ws = None
         self.viewmats = viewmats.to(device)
         self.Ks = Ks.to(device)
         if targets is None:
@@ -459,6 +514,50 @@ class Trainer:
         out = self._gaussian_moments()
         if getattr(self, "bilateral_grid", False):
             out["bil_grids"] = [self.bil_opt.exp_avg[0], self.bil_opt.exp_avg_sq[0]]
+        if getattr(self, "pose_opt", False):
+            self.sync()
+            out["pose_embeds"] = [self._pose_m, self._pose_v]
+        return out
+
+    # ----------------------------------------------------------- pose_opt
+    @property
+    def pose_active(self) -> bool:
+        """The step renders through pose.pose_apply (pose_opt or pose_noise)."""
+        return getattr(self, "pose_opt", False) or getattr(self, "pose_noise", 0.0) > 0.0
+
+    def pose_lr_at(self, it: int) -> float:
+        """The pose optimizer's learning rate at step `it`: pose_opt_lr sqrt(BS),
+        on ExponentialLR(0.01 ** (1 / max_steps)) when max_steps is set."""
+        from .pose import pose_lr
+        return pose_lr(it, self.max_steps, self.pose_lr)
+
+    def _pose_workspace(self):
+        """The projection backward's pose partials, sized for the Gaussians."""
+        from .pose import pose_workspace
+        n = self.params["means"].shape[0]
+        if self._pose_ws is None or self._pose_ws.numel() < 16 * ((n + 255) // 256):
+            self._pose_ws = pose_workspace(n, self.device)
+        return self._pose_ws
+
+    def _pose_viewmat(self, base, cam_index, out=None):
+        """Launch (a): `base` [1,4,4] adjusted by the noise and embedding rows of
+        the device index `cam_index` into `out` (default: the step's buffer)."""
+        from .pose import pose_apply
+        return pose_apply(base, cam_index, self.pose_embeds if self.pose_opt else None,
+                          self.pose_noise_table, out=self._pose_vm if out is None else out)
+
+    @torch.no_grad()
+    def adjusted_viewmats(self, ids=None):
+        """The refined view matrices [len(ids), 4, 4] of the training cameras
+        `ids` (default: all): T(embeds)^-1 T(noise)^-1 viewmat."""
+        self.sync()
+        ids = list(range(len(self.viewmats))) if ids is None else [int(i) for i in ids]
+        vms = self.viewmats.float().contiguous()
+        if not self.pose_active:
+            return vms[ids].clone()
+        out = torch.empty(len(ids), 4, 4, device=vms.device)
+        for k, ci in enumerate(ids):
+            self._pose_viewmat(vms[ci:ci + 1], self._pose_index[ci:ci + 1], out=out[k:k + 1])
         return out
 
     def _gaussian_moments(self):
@@ -584,12 +683,15 @@ class Trainer:
                                   normal_lambda=nl, dist_lambda=dl, _depth_image=True)
 
     def render(self, ci: int, sh_degree: Optional[int] = None,
-               fusion: Optional[_wrapper.StepFusion] = None, world_ci=None, geometry=None):
+               fusion: Optional[_wrapper.StepFusion] = None, world_ci=None, geometry=None,
+               viewmats=None):
         """Render camera `ci`; `fusion` (a training step's StepFusion) goes to
         the nodes whose backward hands their gradients to the optimizer.
         `geometry` (2DGS): the step's (normal_lambda, dist_lambda); with one
         non-zero the normal and distortion images are rendered too
         (meta["_geometry"], geometry_loss).
+        `viewmats` (3DGS, one rank): a [1,4,4] view matrix instead of camera
+        `ci`'s own (a pose_opt step's adjusted one).
         Gaussian-sharded: a collective -- every rank renders its own camera
         with all ranks' Gaussians (`world_ci`: see world_cameras)."""
         p = self.params
@@ -638,7 +740,8 @@ class Trainer:
             return rasterization(
                 p["means"], p["quats"], scales, opac,
                 (p["sh0"], p["shN"]) if self.fused else torch.cat([p["sh0"], p["shN"]], 1),
-                self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1], self.width, self.height,
+                self.viewmats[ci:ci + 1] if viewmats is None else viewmats,
+                self.Ks[ci:ci + 1], self.width, self.height,
                 sh_degree=deg, packed=getattr(self, "packed", False), near_plane=0.01,
                 far_plane=1e10, radius_clip=0.0, rasterize_mode=self.rasterize_mode,
                 absgrad=absgrad,
@@ -721,7 +824,12 @@ class Trainer:
             self._set_means_lr(self.lrs[0] * (0.01 ** (1.0 / self.max_steps)) ** it)
         fusion = self._make_fusion()
         terms = self.geometry_terms_at(it)
-        colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion, geometry=terms)
+        pose_vm = None
+        if self.pose_active:  # launch (a): this step's view matrix
+            pose_vm = self._pose_viewmat(_wrapper._f32c(self.viewmats[ci:ci + 1]),
+                                         self._pose_index[ci:ci + 1])
+        colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion, geometry=terms,
+                                           viewmats=pose_vm)
         if self.model == "3dgs":
             # DefaultStrategy.step_pre_backward: the means2d gradient is
             # captured by a hook (retain_grad would clone it into .grad)
@@ -793,8 +901,24 @@ class Trainer:
         if tv is not None:
             self.bil_opt.step()
             self.bil_opt.zero_grad()
+        if getattr(self, "pose_opt", False):
+            self._pose_step(it, ci)
         self.last_meta = meta
         return loss
+
+    def _pose_step(self, it: int, ci: int):
+        """Launch (c) of an eager step: the pose gradient from the projection
+        backward's partials and the pose Adam over the whole table."""
+        from .pose import pose_bwd_adam
+        if not self.geom_applied:
+            raise RuntimeError("pose_opt: the projection backward did not run the geometry "
+                               "Adam, so it formed no pose gradient (a loss term outside the "
+                               "render reached the geometry parameters?)")
+        self.pose_step_count += 1
+        pose_bwd_adam(self._pose_ws, self.params["means"].shape[0],
+                      _wrapper._f32c(self.viewmats[ci:ci + 1]), self._pose_index[ci:ci + 1],
+                      self.pose_embeds, self._pose_m, self._pose_v, self.pose_lr_at(it),
+                      self.pose_opt_reg, self.pose_step_count, noise=self.pose_noise_table)
 
     def _regularise(self, loss):
         """simple_trainer.py:671-681: the opacity / scale regularisers on the raw
@@ -825,6 +949,8 @@ class Trainer:
         ga = None
         if getattr(self, "geom_in_proj", False) and isinstance(self.opt, FusedAdam):
             ga = self.geom_adam_in_backward(self.opt.step_count + 1)
+            if getattr(self, "pose_opt", False):
+                ga.pose_ws = self._pose_workspace()
         if fa is None and not geom:
             return None
         return _wrapper.StepFusion(sh_adam=fa, geom=geom, geom_adam=ga)

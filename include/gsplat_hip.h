@@ -55,7 +55,11 @@ const char *gsplat_hip_last_error(void);
  *     trainer's normal-consistency and distortion terms).
  * 37: gsplat_hip_bilagrid_slice_fwd / _bwd / _workspace_bytes and
  *     gsplat_hip_bilagrid_tv_fwd / _bwd / _workspace_bytes (the 3DGS trainer's
- *     bilateral-grid colour correction). */
+ *     bilateral-grid colour correction).
+ * 38: gsplat_hip_pose_apply, gsplat_hip_pose_bwd_adam,
+ *     gsplat_hip_pose_workspace_bytes, gsplat_hip_projection_bwd_adam_pose and
+ *     gsplat_hip_pose_adjust_fwd / _bwd (the 3DGS trainer's camera pose
+ *     optimisation); new entries only. */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1059,6 +1063,65 @@ int gsplat_hip_bilagrid_tv_fwd(int N, int L, int Hg, int Wg, const float *grids,
                                float *out, void *workspace, void *stream);
 int gsplat_hip_bilagrid_tv_bwd(int N, int L, int Hg, int Wg, const float *grids, float scale,
                                const float *g_loss, float *v_grids, void *stream);
+
+/* Camera pose optimisation (ABI 38; examples/utils.py CameraOptModule and
+ * simple_trainer.py pose_opt / pose_noise, csrc/pose.hip).
+ * A pose row is e[9] = (dx[3], d6[6]).  With a1 = d6[0:3] + (1,0,0),
+ * a2 = d6[3:6] + (0,1,0): b1 = a1 / max(|a1|, 1e-12),
+ * b2 = normalize(a2 - (b1 . a2) b1) with the same clamp, b3 = b1 x b2, R the
+ * matrix of rows b1, b2, b3, T = [[R, dx], [0, 1]].  The reference adjusts
+ * camera-to-world matrices, c2w' = c2w T; a view matrix is adjusted by
+ * viewmat' = T^-1 viewmat, T^-1 = [[R^T, -R^T dx], [0, 1]] (the reference's
+ * inv(c2w T) up to fp32 rounding; view matrices are affine: bottom row 0 0 0 1).
+ * A zero row reproduces its input bit for bit.
+ *
+ * gsplat_hip_pose_apply: one launch.  base_viewmat[16] and cam_index[1]
+ *   (device int64, clamped to [0, n_images)) are read on the device; embeds
+ *   and noise are [n_images, 9] tables, either may be NULL (identity).
+ *   viewmat_out[16] = T(embeds[cam])^-1 T(noise[cam])^-1 base_viewmat (the
+ *   reference's c2w T_noise T_adj); camtoworld_out[16] (may be NULL) its rigid
+ *   inverse.  viewmat_out must not alias base_viewmat.
+ * gsplat_hip_projection_bwd_adam_pose: gsplat_hip_projection_bwd_adam (same
+ *   arguments, bit-identical parameter and moment updates) that also writes,
+ *   per 256-Gaussian block b, 16 floats to pose_workspace[b]: the block's sums
+ *   of dL/dviewmat (rows 0-2 of the 4x4, 12 values: element 4 i + j), then of
+ *   v_dirs over the Gaussians with radii > 0 (3 values), then 0.  Every row is
+ *   written (no atomics, no zeroing launch); the workspace is
+ *   gsplat_hip_pose_workspace_bytes(N) of uninitialised memory.
+ * gsplat_hip_pose_bwd_adam: one workgroup.  Adds the workspace rows of the N
+ *   Gaussians' blocks in a fixed order (bit-identical between calls), chains
+ *   dL/dviewmat' and the camera-centre gradient of the SH colours
+ *   (-sum v_dirs) back to (dx, d6) of row cam_index[0] of embeds, and applies
+ *   torch.optim.Adam(weight_decay) -- the L2 form g += weight_decay * w --
+ *   to the WHOLE table in place: rows of other cameras get g = weight_decay * w.
+ *   Factors: lr and the 1-based step, or hyper_device f32[2] =
+ *   (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) (then lr / step are unused).
+ *   skip_device (may be NULL): non-zero = void step, nothing is changed.
+ * gsplat_hip_pose_adjust_fwd / _bwd: out[B,4,4] = camtoworlds[B,4,4] T(deltas[B,9])
+ *   and v_deltas[B,9] from v_out[B,4,4] (CameraOptModule.forward after the
+ *   embedding lookup); one lane per matrix, every element written. */
+int64_t gsplat_hip_pose_workspace_bytes(int N);
+int gsplat_hip_pose_apply(int n_images, const float *base_viewmat, const int64_t *cam_index,
+                          const float *embeds, const float *noise, float *viewmat_out,
+                          float *camtoworld_out, void *stream);
+int gsplat_hip_projection_bwd_adam_pose(
+    int N, const float *means, const float *quats, const float *scales, const float *viewmats,
+    const float *Ks, int width, int height, float eps2d, const int32_t *radii,
+    const float *conics, const float *v_means2d, const float *v_depths, const float *v_conics,
+    const float *v_dirs, const float *v_opac, const float *opac, float *const *params,
+    float *const *exp_avgs, float *const *exp_avg_sqs, const float *lrs, float beta1,
+    float beta2, float eps, int step, const float *hyper_device, const int32_t *skip_device,
+    void *pose_workspace, void *stream);
+int gsplat_hip_pose_bwd_adam(int n_images, int N, const void *workspace,
+                             const float *base_viewmat, const int64_t *cam_index, float *embeds,
+                             const float *noise, float *exp_avg, float *exp_avg_sq, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int step,
+                             const float *hyper_device, const int32_t *skip_device,
+                             void *stream);
+int gsplat_hip_pose_adjust_fwd(int64_t B, const float *camtoworlds, const float *deltas,
+                               float *out, void *stream);
+int gsplat_hip_pose_adjust_bwd(int64_t B, const float *camtoworlds, const float *deltas,
+                               const float *v_out, float *v_deltas, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
