@@ -22,6 +22,7 @@ from ._wrapper_indices import (
     rasterize_to_indices_in_range_2dgs,
 )
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
+from .depth_loss import sparse_depth_loss
 from .losses import geometry_loss_2dgs
 from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
@@ -38,6 +39,7 @@ __all__ = [
     "rasterization_2dgs",
     "depth_to_normal",
     "geometry_loss_2dgs",
+    "sparse_depth_loss",
     "bilagrid_slice",
     "bilagrid_tv_loss",
     "bilagrid_identity",

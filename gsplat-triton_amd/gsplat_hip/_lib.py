@@ -169,6 +169,11 @@ _SIGS = {
                                              _i32, _f, _f, _p, _p, _p]),
     "gsplat_hip_geom_loss_2dgs_bwd": (_i32, [_i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _i32,
                                              _i32, _f, _f, _p, _p, _p, _i64, _i32, _p, _p]),
+    "gsplat_hip_depth_loss_workspace_bytes": (_i64, [_i64]),
+    "gsplat_hip_depth_loss_fwd": (_i32, [_i32, _i32, _p, _i64, _p, _i64, _p, _p, _i32, _i64, _p,
+                                         _p, _p, _p, _p]),
+    "gsplat_hip_depth_loss_bwd": (_i32, [_i32, _i32, _p, _i64, _p, _i64, _p, _p, _i32, _i64, _p,
+                                         _p, _p, _p, _i64, _i32, _i32, _p, _p]),
     "gsplat_hip_bilagrid_slice_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "gsplat_hip_bilagrid_slice_fwd": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p,
                                              _p, _p]),

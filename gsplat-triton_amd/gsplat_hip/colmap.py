@@ -399,10 +399,15 @@ class Parser:
 
 
 class Dataset:
-    """colmap.py:336-440: every `test_every`-th image is a test image."""
+    """colmap.py:336-440: every `test_every`-th image is a test image.
+    `load_depths` (colmap.py:342-347, 394-415): items also hold the image's
+    SfM points projected into it, "points" [M, 2] (pixels) and "depths" [M]
+    (camera z) -- Trainer(depth_points=...)'s input."""
 
-    def __init__(self, parser: Parser, split: str = "train", patch_size: Optional[int] = None):
+    def __init__(self, parser: Parser, split: str = "train", patch_size: Optional[int] = None,
+                 load_depths: bool = False):
         self.parser, self.split, self.patch_size = parser, split, patch_size
+        self.load_depths = bool(load_depths)
         idx = np.arange(len(parser.image_names))
         self.indices = idx[idx % parser.test_every != 0] if split == "train" else \
             idx[idx % parser.test_every == 0]
@@ -428,7 +433,24 @@ class Dataset:
             image = image[y:y + self.patch_size, x:x + self.patch_size]
             K[0, 2] -= x
             K[1, 2] -= y
-        return {"K": torch.from_numpy(K).float(),
-                "camtoworld": torch.from_numpy(self.parser.camtoworlds[index]).float(),
+        camtoworld = self.parser.camtoworlds[index]
+        data = {"K": torch.from_numpy(K).float(),
+                "camtoworld": torch.from_numpy(camtoworld).float(),
                 "image": torch.from_numpy(np.ascontiguousarray(image)).float(),
                 "image_id": item}
+        if self.load_depths:
+            # the image's points in its camera frame, projected with the
+            # (crop-shifted) K; kept inside the image and in front of the camera
+            w2c = np.linalg.inv(camtoworld)
+            ids = self.parser.point_indices.get(self.parser.image_names[index],
+                                                np.zeros(0, np.int32))
+            cam = (w2c[:3, :3] @ self.parser.points[ids].T + w2c[:3, 3:4]).T
+            proj = (K @ cam.T).T
+            with np.errstate(divide="ignore", invalid="ignore"):
+                points = proj[:, :2] / proj[:, 2:3]
+            depths = cam[:, 2]
+            keep = ((points[:, 0] >= 0) & (points[:, 0] < image.shape[1]) & (points[:, 1] >= 0)
+                    & (points[:, 1] < image.shape[0]) & (depths > 0))
+            data["points"] = torch.from_numpy(points[keep]).float().reshape(-1, 2)
+            data["depths"] = torch.from_numpy(depths[keep]).float()
+        return data

@@ -250,7 +250,12 @@ class GraphStep:
         # the render and the loss and 10 x tv added after it (ring bypassed),
         # the grids' Adam factors at floats [BIL, BIL + 2) of the block
         self.bil = bool(getattr(tr, "bilateral_grid", False))
-        self.ring_now = self.ring_loss and not self.bil
+        # sparse depth supervision (Trainer(depth_loss=True)): the RGB+D render,
+        # the photometric loss and the depth term of the block's camera as
+        # one node (Trainer.depth_losses), their sum formed after it (ring
+        # bypassed)
+        self.depth = bool(getattr(tr, "depth_loss", False))
+        self.ring_now = self.ring_loss and not self.bil and not self.depth
         # camera pose optimisation (Trainer(pose_opt=True) / pose_noise): the
         # step's view matrix made from the block's by pose.pose_apply right
         # after the fetch, the pose Adam (its factors at floats [POSE, POSE + 2))
@@ -355,16 +360,19 @@ class GraphStep:
         else:
             with _wrapper.fwd_split(getattr(tr, "split_div", None),
                                     getattr(tr, "split_threshold", None)):
-                colors, _, meta = rasterization(
+                colors, alphas, meta = rasterization(
                     p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), vm, self.K,
                     tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
                     far_plane=1e10, radius_clip=0.0,
-                    rasterize_mode=getattr(tr, "rasterize_mode", "classic"), _fusion=fusion,
+                    rasterize_mode=getattr(tr, "rasterize_mode", "classic"),
+                    render_mode="RGB+D" if self.depth else "RGB", _fusion=fusion,
                     _isect_capacity=self.capacity, _isect_status=self.status,
                     _isect_report=(self.ring_out.dev, self.slot), _isect_ids=False, **dkw)
             meta["means2d"].register_hook(lambda g: grad_box.__setitem__("g", g))
         tv = None
-        if self.bil:  # Trainer._eager_step's slice, the grid chosen on the device
+        if self.depth:
+            rgbd = colors
+        elif self.bil:  # Trainer._eager_step's slice, the grid chosen on the device
             from .bilagrid import _slice_tv
             colors, tv = _slice_tv(tr.bil_grids, colors, self.cam, tr.BIL_TV_WEIGHT)
         vote = None
@@ -373,10 +381,15 @@ class GraphStep:
             from . import distributed as gdist
             vote = dist.all_reduce(self.status, op=dist.ReduceOp.MAX, async_op=True,
                                    group=gdist.current_capture_group())
-        loss = l1_ssim_loss(
-            colors, tr.targets, tr.ssim_lambda, gt_index=self.cam,
-            _out_ring=(self.loss_ring, self.seq) if self.ring_now else None,
-            _channels=3 if tr.model == "2dgs" else None)
+        if self.depth:  # Trainer._eager_step's losses, image and target chosen on the device
+            photo, term, tv = tr.depth_losses(rgbd, alphas, tr.targets, self.cam,
+                                              gt_index=self.cam)
+            loss = photo + term
+        else:
+            loss = l1_ssim_loss(
+                colors, tr.targets, tr.ssim_lambda, gt_index=self.cam,
+                _out_ring=(self.loss_ring, self.seq) if self.ring_now else None,
+                _channels=3 if tr.model == "2dgs" else None)
         if any(terms):
             loss = loss + tr.geometry_loss(meta, self.K, terms)
         if tv is not None:
@@ -482,7 +495,8 @@ class GraphStep:
         if self.pose:
             tr._pose_workspace()  # sized for the Gaussians, allocated outside the capture
         torch.cuda.synchronize(self.dev)
-        self.ring_now = self.ring_loss and not any(self.terms) and not self.bil
+        self.ring_now = (self.ring_loss and not any(self.terms) and not self.bil
+                         and not self.depth)
         try:
             # warm-up on a side stream (torch's capture recipe) as a VOID
             # step: the flag makes every state update a no-op.  Only before

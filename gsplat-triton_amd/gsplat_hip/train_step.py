@@ -31,6 +31,15 @@ pose.pose_bwd_adam turns them into the row's gradient and steps the table's
 dense Adam with L2 weight decay -- no view matrix requires grad, the step
 stays fused and graph-replayed.  evaluate() renders the cameras unadjusted.
 
+`depth_loss=True` (3DGS, simple_trainer.py `depth_loss` / `depth_lambda`):
+the step renders RGB+D and adds depth_lambda * scene_scale * the mean
+disparity L1 at the image's projected SfM points (`depth_points`, one
+(points, depths) pair per training image as colmap.Dataset(load_depths=True)
+gives them; kept as CSR tables on the device).  The photometric loss and the
+depth term are one autograd node (depth_loss.l1_ssim_depth_loss): one extra
+launch forward, a zero fill and a scatter backward, the image chosen by a
+device index, so the step stays fused and graph-replayed.
+
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
 DefaultStrategy schedule after the optimizer step (simple_trainer.py:808-826
 -> gsplat/strategy/default.py:164-211): refine (grow + prune, one HIP
@@ -209,9 +218,32 @@ class Trainer:
                  dist_lambda: float = 1e-2, dist_start_iter: int = 3000,
                  bilateral_grid: bool = False, bilateral_grid_shape=(16, 16, 8),
                  pose_opt: bool = False, pose_opt_lr: float = 1e-5, pose_opt_reg: float = 1e-6,
-                 pose_noise: float = 0.0):
+                 pose_noise: float = 0.0, depth_loss: bool = False, depth_lambda: float = 1e-2,
+                 depth_points=None):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # simple_trainer.py depth_loss / depth_lambda (:163-165, 647-665): the
+        # disparity L1 at each image's projected SfM points (depth_loss.py),
+        # added to the loss times depth_lambda * scene_scale; the step then
+        # renders RGB+D.  The one-GPU dense fused 3DGS trainer only
+        self.depth_loss, self.depth_lambda = bool(depth_loss), float(depth_lambda)
+        if self.depth_loss:
+            off = [name for name, on in (
+                ("model='2dgs'", model != "3dgs"), ("packed", packed),
+                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
+                ("gaussian_shard", gaussian_shard),
+                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
+                ("fused=False", not fused)) if on]
+            if off:
+                raise NotImplementedError(
+                    "depth_loss: the one-GPU dense fused 3DGS trainer only; not with "
+                    f"{', '.join(off)}")
+            if depth_points is None:
+                raise ValueError("depth_loss: depth_points, one (points [M, 2], depths [M]) per "
+                                 "training image, is required")
+            if len(depth_points) != len(viewmats):
+                raise ValueError(f"depth_loss: {len(depth_points)} depth_points entries for "
+                                 f"{len(viewmats)} training images")
         # simple_trainer.py pose_opt / pose_opt_lr / pose_opt_reg / pose_noise:
         # a pose row per training image refined by its own Adam (pose.py); the
         # step stays fused: only where the geometry Adam runs in the
@@ -427,6 +459,13 @@ class Trainer:
             self._pose_vm = torch.empty(1, 4, 4, device=device)  # the step's view matrix
             self._pose_index = torch.arange(n_img, dtype=torch.int64, device=device)
             self._pose_ws = None
+        if self.depth_loss:
+            # the images' points as CSR tables on the device, built once; the
+            # step names its image by a device index (the captured step: the
+            # camera index of its input block)
+            from .depth_loss import DepthPoints
+            self.depth_table = DepthPoints(depth_points, device)
+            self._depth_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
         self.viewmats = viewmats.to(device)
         self.Ks = Ks.to(device)
         if targets is None:
@@ -735,18 +774,42 @@ class Trainer:
         if getattr(self, "gshard", False):
             dkw = dict(distributed=True, _world_cameras=self.world_cameras(ci, world_ci),
                        _world_counts=self._n_world)
+        depth = getattr(self, "depth_loss", False)
         with _wrapper.fwd_split(getattr(self, "split_div", None),
                                 getattr(self, "split_threshold", None)):
-            return rasterization(
+            rc, ra, meta = rasterization(
                 p["means"], p["quats"], scales, opac,
                 (p["sh0"], p["shN"]) if self.fused else torch.cat([p["sh0"], p["shN"]], 1),
                 self.viewmats[ci:ci + 1] if viewmats is None else viewmats,
                 self.Ks[ci:ci + 1], self.width, self.height,
                 sh_degree=deg, packed=getattr(self, "packed", False), near_plane=0.01,
                 far_plane=1e10, radius_clip=0.0, rasterize_mode=self.rasterize_mode,
-                absgrad=absgrad,
+                absgrad=absgrad, render_mode="RGB+D" if depth else "RGB",
                 sparse_grad=getattr(self, "sparse_grad", False), _colors_ready=hook,
                 _fusion=fusion, **dkw)
+        if depth:  # the losses read the RGB+D render in place (depth_losses)
+            meta["_rgbd"] = rc
+            return rc[..., :3], ra, meta
+        return rc, ra, meta
+
+    def depth_losses(self, rgbd, alphas, gt, cam_index, gt_index=None):
+        """(photometric loss, depth_lambda * scene_scale * the depth term, the
+        bilateral grids' tv or None) of an RGB+D render [1,H,W,4] for the image
+        of the device index `cam_index`.  Without the bilateral grid the two
+        losses are one autograd node (depth_loss.l1_ssim_depth_loss); with it
+        the grid is applied to the colour channels alone."""
+        from . import depth_loss as _dl
+        weight = self.depth_lambda * self.scene_scale
+        if getattr(self, "bilateral_grid", False):
+            from .bilagrid import _slice_tv
+            colors, tv = _slice_tv(self.bil_grids, _dl.colour_channels(rgbd), cam_index,
+                                   self.BIL_TV_WEIGHT)
+            photo = l1_ssim_loss(colors, gt, self.ssim_lambda, gt_index=gt_index)
+            term = _dl.table_depth_loss(rgbd, alphas, self.depth_table, cam_index, 3)
+            return photo, weight * term, tv
+        photo, term = _dl.l1_ssim_depth_loss(rgbd, alphas, gt, self.ssim_lambda,
+                                             self.depth_table, cam_index, gt_index=gt_index)
+        return photo, weight * term, None
 
     def _tune_split(self, it: int):
         """Once, before the first step (and so before a graph capture freezes
@@ -836,14 +899,20 @@ class Trainer:
             meta["means2d"].register_hook(lambda g: meta.__setitem__("means2d_grad", g))
         gt = self.targets[ci:ci + 1]
         tv = None
+        depth = getattr(self, "depth_loss", False)
         if getattr(self, "bilateral_grid", False):
             # simple_trainer.py:620-630, 663-665: the camera's grid applied to
             # the render, 10 x the grids' total variation added to the loss
             from .bilagrid import _slice_tv, bilagrid_lr
             self.bil_opt.lrs[0] = bilagrid_lr(it, self.max_steps, self.bil_lr)
-            colors, tv = _slice_tv(self.bil_grids, colors, self._bil_index[ci:ci + 1],
-                                   self.BIL_TV_WEIGHT)
-        if self.fused and "_rgbd" in meta:  # 2DGS: the RGB+D render in place
+            if not depth:
+                colors, tv = _slice_tv(self.bil_grids, colors, self._bil_index[ci:ci + 1],
+                                       self.BIL_TV_WEIGHT)
+        if depth:  # simple_trainer.py:647-665: the photometric loss and the depth term
+            photo, term, tv = self.depth_losses(meta["_rgbd"], alphas, gt,
+                                                self._depth_index[ci:ci + 1])
+            loss = photo + term
+        elif self.fused and "_rgbd" in meta:  # 2DGS: the RGB+D render in place
             loss = l1_ssim_loss(meta["_rgbd"], gt, self.ssim_lambda, _channels=3)
         elif self.fused:
             loss = l1_ssim_loss(colors, gt, self.ssim_lambda)

@@ -59,7 +59,9 @@ const char *gsplat_hip_last_error(void);
  * 38: gsplat_hip_pose_apply, gsplat_hip_pose_bwd_adam,
  *     gsplat_hip_pose_workspace_bytes, gsplat_hip_projection_bwd_adam_pose and
  *     gsplat_hip_pose_adjust_fwd / _bwd (the 3DGS trainer's camera pose
- *     optimisation); new entries only. */
+ *     optimisation); new entries only.  Added later without a new number
+ *     (new entries only, no signature changed): gsplat_hip_depth_loss_fwd /
+ *     _bwd / _workspace_bytes (the 3DGS trainer's sparse depth supervision). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1019,6 +1021,48 @@ int gsplat_hip_geom_loss_2dgs_bwd(int C, int H, int W, const float *normals, con
                                   const float *g_loss, float *v_normals, float *v_depths,
                                   int64_t v_depth_stride, int zero_rest, float *v_distort,
                                   void *stream);
+
+/* Sparse depth supervision (examples/simple_trainer.py:647-665 depth_loss: the
+ * RGB+ED render's division by alpha, the slice / permute, F.grid_sample(
+ * align_corners=True) at the points, where(d > 0, 1 / d, 0) and F.l1_loss
+ * against 1 / d_gt), fused for one image (csrc/depth_loss.hip):
+ *   ed_j = sum_k w_k depths[k] / max(alphas[k], 1e-10) over the four bilinear
+ *   corners floor / floor + 1 of (x_j, y_j) in pixel units, a corner outside
+ *   the image contributing 0; disp_j = ed_j > 0 ? 1 / ed_j : 0;
+ *   out[0] = mean_j |disp_j - 1 / d_gt_j|, and 0 for an image without points
+ *   (torch: NaN).  alphas == NULL: depths is already the expected depth.
+ * depths[H,W] / alphas[H,W] with depth_stride / alpha_stride floats from pixel
+ * to pixel (an RGB+D render's channel 3 read in place).  The points of every
+ * image are CSR tables on the device: points[sum M, 3] rows (x, y, d_gt),
+ * offsets int32[n_images + 1]; the image is cam_index[0] (device int64,
+ * clamped to [0, n_images)), read on the device; max_points >= the largest M
+ * of the table sizes the grid (an image's count is clamped to it).
+ * fwd: one launch.  unit[max_points]: d out[0] / d ed_j of the image's points
+ *   (0 where ed_j <= 0 or disp_j == 1 / d_gt_j, as torch's sign).  The sum is
+ *   reduced in a fixed order (bit-identical between calls).  workspace =
+ *   gsplat_hip_depth_loss_workspace_bytes(max_points), 16-B aligned, its
+ *   first 4 bytes ZERO before the first call; every call leaves them zero.
+ * bwd: for dL = g_loss[0] (device scalar) the gradient is ADDED with float
+ *   atomics (points share pixels) to channel `channel` of v_image
+ *   [H,W,v_image_stride] and, with alphas, to v_alphas[H,W]:
+ *   d ed = dL unit_j; d depths[k] = w_k d ed / max(alphas[k], 1e-10);
+ *   d alphas[k] = -w_k d ed depths[k] / alphas[k]^2 where alphas[k] > 1e-10.
+ *   v_alphas is zero-filled by a kernel first; zero_image = 1 zero-fills all
+ *   of v_image the same way, 0 leaves it to the caller (the render-shaped
+ *   gradient of gsplat_hip_l1_ssim_loss_fused_fwd, zero in that channel).
+ *   No allocation, no sync, no memset node. */
+int64_t gsplat_hip_depth_loss_workspace_bytes(int64_t max_points);
+int gsplat_hip_depth_loss_fwd(int H, int W, const float *depths, int64_t depth_stride,
+                              const float *alphas, int64_t alpha_stride, const float *points,
+                              const int32_t *offsets, int n_images, int64_t max_points,
+                              const int64_t *cam_index, float *out, float *unit,
+                              void *workspace, void *stream);
+int gsplat_hip_depth_loss_bwd(int H, int W, const float *depths, int64_t depth_stride,
+                              const float *alphas, int64_t alpha_stride, const float *points,
+                              const int32_t *offsets, int n_images, int64_t max_points,
+                              const int64_t *cam_index, const float *unit, const float *g_loss,
+                              float *v_image, int64_t v_image_stride, int channel,
+                              int zero_image, float *v_alphas, void *stream);
 
 /* Bilateral-grid colour correction (ABI 37; examples/lib_bilagrid.py
  * BilateralGrid / slice / total_variation_loss, fused in csrc/bilagrid.hip).
