@@ -21,6 +21,7 @@ from ._wrapper_indices import (
     rasterize_to_indices_in_range,
     rasterize_to_indices_in_range_2dgs,
 )
+from .appearance import appearance_colors
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
 from .depth_loss import sparse_depth_loss
 from .losses import geometry_loss_2dgs
@@ -45,6 +46,7 @@ __all__ = [
     "bilagrid_identity",
     "bilagrid_lr",
     "pose_adjust",
+    "appearance_colors",
     "quat_scale_to_covar_preci",
     "compute_relocation",
     "adam",

@@ -187,6 +187,7 @@ class GraphStep:
     MAX_WORLD = 8  # cameras of a Gaussian-sharded step in the block
     BIL = 60  # floats [60, 62) of the block: the bilateral grids' Adam factors
     POSE = 62  # floats [62, 64): the pose table's Adam factors (Trainer(pose_opt=True))
+    APP = 56  # floats [56, 60): the appearance module's Adam factors (Trainer(app_opt=True))
 
     def __init__(self, tr, capacity=None, headroom=1.25, lag=2):
         assert graphable(tr), "GraphStep: a fused 3DGS trainer (graph_step.graphable)"
@@ -262,6 +263,11 @@ class GraphStep:
         # a launch after the other updates
         self.pose = bool(getattr(tr, "pose_opt", False))
         self.pose_any = bool(getattr(tr, "pose_active", False))
+        # appearance optimisation (Trainer(app_opt=True)): the colours from the
+        # appearance MLP after the projection, the embedding row chosen by the
+        # block's camera index, the module's two Adam optimizers (factors at
+        # floats [APP, APP + 4)) a launch after the other updates
+        self.app = bool(getattr(tr, "app_opt", False))
         self._warmed = set()  # the active-term sets a warm-up step has run for
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # sticky overflow flag
         self.ring_in = _Mapped(self.RING * self.SLOT)
@@ -294,7 +300,7 @@ class GraphStep:
             idx = [i for sel in self.tr.opt.launch_plan() for i in sel]
             return idx, 2 * len(idx)
         names = list(self.tr.params)
-        sh = {names.index("sh0"), names.index("shN")}
+        sh = {names.index(k) for k in ("sh0", "shN") if k in names}
         idx = [i for i in range(self.n_groups) if not (self.tr.sh_adam_in_bwd and i in sh)]
         return idx, 2 * len(idx)
 
@@ -358,11 +364,17 @@ class GraphStep:
             # (a hook keeping a reference would make AccumulateGrad clone the
             # gradient -- a memcpy node in the graph)
         else:
+            coeffs, deg_r = None, deg
+            if self.app:  # Trainer.render's colours, the embedding row chosen on the device
+                coeffs, deg_r = p["colors"], None
+                dkw["_app"] = tr._app_colors(vm, deg, self.cam, fusion)
+            else:
+                coeffs = (p["sh0"], p["shN"])
             with _wrapper.fwd_split(getattr(tr, "split_div", None),
                                     getattr(tr, "split_threshold", None)):
                 colors, alphas, meta = rasterization(
-                    p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), vm, self.K,
-                    tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
+                    p["means"], p["quats"], scales, opac, coeffs, vm, self.K,
+                    tr.width, tr.height, sh_degree=deg_r, packed=False, near_plane=0.01,
                     far_plane=1e10, radius_clip=0.0,
                     rasterize_mode=getattr(tr, "rasterize_mode", "classic"),
                     render_mode="RGB+D" if self.depth else "RGB", _fusion=fusion,
@@ -440,6 +452,8 @@ class GraphStep:
                           tr._pose_m, tr._pose_v, 0.0, tr.pose_opt_reg, 1,
                           noise=tr.pose_noise_table, hyper=self.scal[self.POSE:self.POSE + 2],
                           skip=self.status)
+        if self.app:  # Trainer._app_step, factors and void flag on the device
+            tr._app_step(self.cam, hyper=self.scal[self.APP:self.APP + 4], skip=self.status)
         if getattr(tr, "mcmc", False):
             # MCMCStrategy's position noise after the update (Trainer.mcmc_noise):
             # the step and its scale from the block (scale 0 on refine steps,
@@ -494,6 +508,8 @@ class GraphStep:
             tr.opt.wait()  # an eager step's deferred all-gathers
         if self.pose:
             tr._pose_workspace()  # sized for the Gaussians, allocated outside the capture
+        if self.app:
+            tr._app_workspace()  # likewise
         torch.cuda.synchronize(self.dev)
         self.ring_now = (self.ring_loss and not any(self.terms) and not self.bil
                          and not self.depth)
@@ -594,6 +610,11 @@ class GraphStep:
             from .pose import BETAS
             f[self.POSE], f[self.POSE + 1] = adam_factors([tr.pose_lr_at(it)], BETAS,
                                                           tr.pose_step_count + 1)[0]
+        if self.app:  # torch's Adam for the head (lr) and the embedding table (10 x lr)
+            from .appearance import BETAS as APP_BETAS, EMBED_LR_MULT
+            (sh_, ib_), (se_, _) = adam_factors([tr.app_lr, tr.app_lr * EMBED_LR_MULT],
+                                                APP_BETAS, tr.app_step_count + 1)
+            f[self.APP:self.APP + 4] = (sh_, ib_, se_, 0.0)
         ci = tr.camera_index(it)
         n = len(self._vm_host)
         world_ci = [(ci - tr.rank + r) % n for r in range(self.W)] if self.gshard else [ci]
@@ -678,6 +699,8 @@ class GraphStep:
             self.tr.bil_opt.step_count += 1
         if self.pose:
             self.tr.pose_step_count += 1
+        if self.app:
+            self.tr.app_step_count += 1
         if self.ring_now:
             ret = self.loss_ring[k % self.LOSS_RING]
         elif ret is None:
@@ -728,6 +751,8 @@ class GraphStep:
             tr.bil_opt.step_count -= len(redo)
         if self.pose:
             tr.pose_step_count -= len(redo)
+        if self.app:
+            tr.app_step_count -= len(redo)
         # (a rank voided by another's overflow keeps at least its capacity)
         self.capacity = max(self.capacity or 0,
                             int(math.ceil(self.max_isects * self.headroom)) + 1)

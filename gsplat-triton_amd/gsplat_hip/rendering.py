@@ -81,6 +81,7 @@ def rasterization(
     _world_cameras=None,
     _world_counts=None,
     _isect_ids: bool = True,
+    _app: Optional[Callable[[Tensor], Tensor]] = None,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Rasterize N 3D Gaussians to C images (gsplat/rendering.py:44-598).
 
@@ -101,7 +102,11 @@ def rasterization(
     read -- are then skipped.  `_isect_ids=False` (with `_isect_capacity`,
     the training step): the sorted isects are emitted as depth ranks only
     when the rasterizer walks ranks -- meta["isect_ids"] / ["flatten_ids"]
-    are then None (12 of 16 bytes per isect not written)."""
+    are then None (12 of 16 bytes per isect not written).  `_app` (a trainer
+    with app_opt, sh_degree None, dense): a callable giving the colours
+    [C, N, 3] from the projection's radii [C, N] -- the appearance MLP run
+    after the projection, so Gaussians no camera sees cost nothing; `colors`
+    is then not read."""
     meta = {}
     N = means.shape[0]
     C = viewmats.shape[0]
@@ -205,7 +210,12 @@ def rasterization(
                                            camera_ids=camera_ids, gaussian_ids=gaussian_ids,
                                            sync=not capped)
 
+    if _app is not None:
+        assert sh_degree is None and not packed and not distributed, "_app: dense, one rank"
+
     def eval_colors(colors):
+        if _app is not None:
+            return _app(radii)
         if packed:  # colours of the nnz pairs (gsplat/rendering.py:368-408)
             if sh_degree is None:
                 colors = colors[gaussian_ids] if colors.dim() == 2 else colors[camera_ids, gaussian_ids]

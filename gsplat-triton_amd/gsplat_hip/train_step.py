@@ -40,6 +40,16 @@ depth term are one autograd node (depth_loss.l1_ssim_depth_loss): one extra
 launch forward, a zero fill and a scatter backward, the image chosen by a
 device index, so the step stays fused and graph-replayed.
 
+`app_opt=True` (3DGS, simple_trainer.py `app_opt` / `app_embed_dim` /
+`app_opt_lr` / `app_opt_reg`): the colours come from the appearance MLP
+(appearance.py) over the groups `features` [N,32] and `colors` [N,3] (logits),
+which replace sh0 / shN, the step's row of `app_embeds` [cameras, 16] and the
+view direction's SH bases at the step's degree; evaluated after the projection
+under its radii mask, the means gradient handed to the geometry Adam as the SH
+backward's is.  One more launch sums the backward's partial sums and steps the
+module's two Adam optimizers (head `app_head`; the table at 10 x the rate with
+weight decay, densely).  evaluate() renders with the zero embedding.
+
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
 DefaultStrategy schedule after the optimizer step (simple_trainer.py:808-826
 -> gsplat/strategy/default.py:164-211): refine (grow + prune, one HIP
@@ -200,7 +210,7 @@ class Trainer:
     BIL_TV_WEIGHT = 10.0  # simple_trainer.py:664: loss += 10 * tv
 
     LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2,
-           "sh0": 2.5e-3, "shN": 2.5e-3 / 20}
+           "sh0": 2.5e-3, "shN": 2.5e-3 / 20, "features": 2.5e-3, "colors": 2.5e-3}
 
     def __init__(self, points, rgbs, viewmats, Ks, width, height, sh_degree=3, device="cuda",
                  seed=42, world_size=1, rank=0, ssim_lambda=0.2, scene_scale=1.0,
@@ -219,9 +229,35 @@ class Trainer:
                  bilateral_grid: bool = False, bilateral_grid_shape=(16, 16, 8),
                  pose_opt: bool = False, pose_opt_lr: float = 1e-5, pose_opt_reg: float = 1e-6,
                  pose_noise: float = 0.0, depth_loss: bool = False, depth_lambda: float = 1e-2,
-                 depth_points=None):
+                 depth_points=None, app_opt: bool = False, app_embed_dim: int = 16,
+                 app_opt_lr: float = 1e-3, app_opt_reg: float = 1e-6):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # simple_trainer.py app_opt / app_embed_dim / app_opt_lr / app_opt_reg
+        # (:243-254, 389-410): the colours from the appearance MLP over
+        # `features` [N,32], a per-image embedding and the view direction's SH
+        # bases, plus the logits `colors` (appearance.py); the one-GPU dense
+        # fused 3DGS trainer only, refused before any device work
+        self.app_opt = bool(app_opt)
+        self.app_opt_reg = float(app_opt_reg)
+        if self.app_opt:
+            off = [name for name, on in (
+                ("pose_opt", bool(pose_opt)), ("pose_noise", float(pose_noise) != 0.0),
+                ("model='2dgs'", model != "3dgs"), ("packed", packed),
+                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
+                ("gaussian_shard", gaussian_shard),
+                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
+                ("fused=False", not fused)) if on]
+            if off:
+                raise NotImplementedError(
+                    "app_opt: the one-GPU dense fused 3DGS trainer only; not with "
+                    f"{', '.join(off)}")
+            if int(app_embed_dim) != 16:
+                raise ValueError("app_opt: app_embed_dim is fixed at 16 (the kernels' layout), "
+                                 f"got {app_embed_dim!r}")
+            if int(sh_degree) != 3:
+                raise ValueError("app_opt: sh_degree is fixed at 3 (the module's 16 bases), "
+                                 f"got {sh_degree!r}")
         # simple_trainer.py depth_loss / depth_lambda (:163-165, 647-665): the
         # disparity L1 at each image's projected SfM points (depth_loss.py),
         # added to the loss times depth_lambda * scene_scale; the step then
@@ -329,7 +365,8 @@ class Trainer:
             scales = torch.log(torch.rand(N, 3, generator=g) * 0.02 + 1e-4)
             quats = F.normalize(torch.randn(N, 4, generator=g), dim=-1)
             opac = torch.logit(torch.rand(N, generator=g).clamp(1e-3, 1 - 1e-3))
-            sh[:, 1:, :] = torch.randn(N, K - 1, 3, generator=g) * 0.01
+            if not self.app_opt:  # (the last draw: the geometry is a plain trainer's)
+                sh[:, 1:, :] = torch.randn(N, K - 1, 3, generator=g) * 0.01
         else:  # simple_trainer.create_splats_with_optimizers, init_type="sfm"
             scales = knn_log_scales(points, init_scale)
             quats = torch.rand(N, 4, generator=g)
@@ -338,6 +375,43 @@ class Trainer:
             "means": points.clone(), "scales": scales, "quats": quats, "opacities": opac,
             "sh0": sh[:, :1].contiguous(), "shN": sh[:, 1:].contiguous(),
         }
+        if self.app_opt:
+            # simple_trainer.py:243-254: `features` U(0,1) [N,32] and the logits
+            # `colors` replace sh0 / shN, ordinary groups of the trainer's Adam
+            # (refine, relocate, sample-add carry them like any parameter).
+            # Every app_opt draw comes from a generator of its own.  The rgbs
+            # are clamped to [1/512, 1 - 1/512] first: the reference's plain
+            # logit gives +-inf for pure black or white SfM points
+            from . import appearance as _app
+            ga_ = torch.Generator().manual_seed(seed + 2027)
+            del self.params["sh0"], self.params["shN"]
+            self.params["features"] = torch.rand(N, _app.FEATURE_DIM, generator=ga_)
+            self.params["colors"] = torch.logit(rgbs.float().clamp(1.0 / 512, 1.0 - 1.0 / 512))
+            n_img = len(viewmats)
+            # utils.py AppearanceOptModule: embeds.weight N(0,1) [n_img,16]; the
+            # head's Linear layers at torch's default initialisation
+            # (U(+-1/sqrt(fan_in)) for weights and biases), the last layer zero.
+            # The head is one flat buffer in the order W1, b1, W2, b2, W3, b3
+            app_embeds = torch.randn(n_img, _app.EMBED_DIM, generator=ga_)
+            bound = 1.0 / math.sqrt(_app.WIDTH)
+            flat = (torch.rand(_app.HEAD_NUMEL, generator=ga_) * 2.0 - 1.0) * bound
+            flat[2 * (_app.WIDTH * _app.WIDTH + _app.WIDTH):] = 0.0
+            self.app_embeds = app_embeds.to(device)
+            self._app_flat = flat.to(device)
+            self.app_head, o_ = [], 0
+            for shape in _app.HEAD_SHAPES:
+                n_ = int(np.prod(shape))
+                self.app_head.append(self._app_flat[o_:o_ + n_].view(shape))
+                o_ += n_
+            self._app_head_m = torch.zeros(_app.HEAD_NUMEL, device=device)
+            self._app_head_v = torch.zeros(_app.HEAD_NUMEL, device=device)
+            self._app_embed_m = torch.zeros(n_img, _app.EMBED_DIM, device=device)
+            self._app_embed_v = torch.zeros(n_img, _app.EMBED_DIM, device=device)
+            self._app_grads = torch.zeros(_app.HEAD_NUMEL + _app.EMBED_DIM, device=device)
+            self._app_index = torch.arange(n_img, dtype=torch.int64, device=device)
+            self._app_ws = None
+            self.app_step_count = 0
+            self.app_lr = float(app_opt_lr) * math.sqrt(world_size)
         # Gaussian-sharded: this rank's Gaussians [rank::world] of the scene
         # initialised as a whole (simple_trainer.py:221-229: knn scales over
         # all points, then the slice), so the shards together are the
@@ -400,7 +474,7 @@ class Trainer:
         # (Gaussian-sharded too: the SH backward sums its shard's gradient over
         # every rank's camera in the kernel before the update)
         self.sh_adam_in_bwd = (fused and not self.sharded and not self.visible_adam
-                               and not self.sparse_grad
+                               and not self.sparse_grad and not self.app_opt
                                and (world_size == 1 or self.gshard)
                                and os.environ.get("GSPLAT_HIP_SH_ADAM_IN_BWD", "1") != "0")
         # the exp / sigmoid VJPs and the means-gradient sum formed inside the
@@ -556,7 +630,58 @@ class Trainer:
         if getattr(self, "pose_opt", False):
             self.sync()
             out["pose_embeds"] = [self._pose_m, self._pose_v]
+        if getattr(self, "app_opt", False):
+            self.sync()
+            out["app_embeds"] = [self._app_embed_m, self._app_embed_v]
+            out["app_head"] = [self._app_head_m, self._app_head_v]  # flat, W1 b1 W2 b2 W3 b3
         return out
+
+    # ------------------------------------------------------------- app_opt
+    def app_state_dict(self):
+        """The appearance module's state under the reference module's keys
+        (utils.py AppearanceOptModule: `embeds.weight`,
+        `color_head.{0,2,4}.{weight,bias}`), so checkpoints interchange."""
+        from .appearance import HEAD_KEYS
+        self.sync()
+        out = {"embeds.weight": self.app_embeds.detach().clone()}
+        for k, t in zip(HEAD_KEYS, self.app_head):
+            out[k] = t.detach().clone()
+        return out
+
+    def _app_colors(self, viewmats, sh_degree, cam_index, fusion):
+        """rasterization(_app=...)'s callable: the colours [1,N,3] of the camera
+        `viewmats` [1,4,4] from the projection's radii (invisible Gaussians are
+        skipped), the embedding row of the device index `cam_index` (None: the
+        zero embedding of the reference's evaluation)."""
+        from .appearance import trainer_colors
+        p = self.params
+        self._app_workspace()
+        vm = viewmats.detach()
+        # the camera centre -R^T t, elementwise on the device
+        campos = -(vm[:, :3, :3] * vm[:, :3, 3:4]).sum(1)
+        return lambda radii: trainer_colors(
+            p["features"], p["colors"], p["means"], radii, campos, self.app_head, sh_degree,
+            None if cam_index is None else self.app_embeds, cam_index, self._app_ws, fusion)
+
+    def _app_workspace(self):
+        """The colour backward's partial sums, sized for the Gaussians."""
+        n = self.params["means"].shape[0]
+        if self._app_ws is None or self._app_ws_n != n:
+            from .appearance import app_workspace
+            self._app_ws, self._app_ws_n = app_workspace(n, 1, self.device), n
+        return self._app_ws
+
+    def _app_step(self, cam_index, hyper=None, skip=None):
+        """After the backward: the ordered sum of the colour backward's partial
+        sums and the module's two Adam optimizers in place (head: lr; the
+        embedding table: 10 x lr with app_opt_reg as weight decay, dense)."""
+        from .appearance import app_reduce_adam
+        app_reduce_adam(self._app_ws, self.params["means"].shape[0], 1, self._app_grads,
+                        self.app_head, self._app_head_m, self._app_head_v, self.app_lr,
+                        self.app_step_count, embeds=self.app_embeds,
+                        embed_ids=cam_index, embed_exp_avg=self._app_embed_m,
+                        embed_exp_avg_sq=self._app_embed_v,
+                        embed_weight_decay=self.app_opt_reg, hyper=hyper, skip=skip)
 
     # ----------------------------------------------------------- pose_opt
     @property
@@ -723,7 +848,7 @@ class Trainer:
 
     def render(self, ci: int, sh_degree: Optional[int] = None,
                fusion: Optional[_wrapper.StepFusion] = None, world_ci=None, geometry=None,
-               viewmats=None):
+               viewmats=None, app_index=None):
         """Render camera `ci`; `fusion` (a training step's StepFusion) goes to
         the nodes whose backward hands their gradients to the optimizer.
         `geometry` (2DGS): the step's (normal_lambda, dist_lambda); with one
@@ -731,6 +856,8 @@ class Trainer:
         (meta["_geometry"], geometry_loss).
         `viewmats` (3DGS, one rank): a [1,4,4] view matrix instead of camera
         `ci`'s own (a pose_opt step's adjusted one).
+        `app_index` (app_opt): the device index [1] of the image whose
+        embedding row colours the render; None: the zero embedding.
         Gaussian-sharded: a collective -- every rank renders its own camera
         with all ranks' Gaussians (`world_ci`: see world_cameras)."""
         p = self.params
@@ -775,14 +902,21 @@ class Trainer:
             dkw = dict(distributed=True, _world_cameras=self.world_cameras(ci, world_ci),
                        _world_counts=self._n_world)
         depth = getattr(self, "depth_loss", False)
+        vms = self.viewmats[ci:ci + 1] if viewmats is None else viewmats
+        if getattr(self, "app_opt", False):
+            # the colours of the appearance MLP at `deg`, rendered as plain
+            # colours (sh_degree None), evaluated after the projection
+            coeffs, deg_r = p["colors"], None
+            dkw["_app"] = self._app_colors(vms, deg, app_index, fusion)
+        else:
+            coeffs, deg_r = ((p["sh0"], p["shN"]) if self.fused
+                             else torch.cat([p["sh0"], p["shN"]], 1)), deg
         with _wrapper.fwd_split(getattr(self, "split_div", None),
                                 getattr(self, "split_threshold", None)):
             rc, ra, meta = rasterization(
-                p["means"], p["quats"], scales, opac,
-                (p["sh0"], p["shN"]) if self.fused else torch.cat([p["sh0"], p["shN"]], 1),
-                self.viewmats[ci:ci + 1] if viewmats is None else viewmats,
+                p["means"], p["quats"], scales, opac, coeffs, vms,
                 self.Ks[ci:ci + 1], self.width, self.height,
-                sh_degree=deg, packed=getattr(self, "packed", False), near_plane=0.01,
+                sh_degree=deg_r, packed=getattr(self, "packed", False), near_plane=0.01,
                 far_plane=1e10, radius_clip=0.0, rasterize_mode=self.rasterize_mode,
                 absgrad=absgrad, render_mode="RGB+D" if depth else "RGB",
                 sparse_grad=getattr(self, "sparse_grad", False), _colors_ready=hook,
@@ -891,8 +1025,10 @@ class Trainer:
         if self.pose_active:  # launch (a): this step's view matrix
             pose_vm = self._pose_viewmat(_wrapper._f32c(self.viewmats[ci:ci + 1]),
                                          self._pose_index[ci:ci + 1])
+        app = getattr(self, "app_opt", False)
         colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion, geometry=terms,
-                                           viewmats=pose_vm)
+                                           viewmats=pose_vm,
+                                           app_index=self._app_index[ci:ci + 1] if app else None)
         if self.model == "3dgs":
             # DefaultStrategy.step_pre_backward: the means2d gradient is
             # captured by a hook (retain_grad would clone it into .grad)
@@ -972,6 +1108,9 @@ class Trainer:
             self.bil_opt.zero_grad()
         if getattr(self, "pose_opt", False):
             self._pose_step(it, ci)
+        if app:  # the module's two optimizers, from the colour backward's partial sums
+            self.app_step_count += 1
+            self._app_step(self._app_index[ci:ci + 1])
         self.last_meta = meta
         return loss
 

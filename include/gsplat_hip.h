@@ -61,7 +61,9 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_pose_adjust_fwd / _bwd (the 3DGS trainer's camera pose
  *     optimisation); new entries only.  Added later without a new number
  *     (new entries only, no signature changed): gsplat_hip_depth_loss_fwd /
- *     _bwd / _workspace_bytes (the 3DGS trainer's sparse depth supervision). */
+ *     _bwd / _workspace_bytes (the 3DGS trainer's sparse depth supervision);
+ *     gsplat_hip_app_colors_fwd / _bwd, gsplat_hip_app_reduce_adam and
+ *     gsplat_hip_app_workspace_bytes (appearance optimisation). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1166,6 +1168,65 @@ int gsplat_hip_pose_adjust_fwd(int64_t B, const float *camtoworlds, const float 
                                float *out, void *stream);
 int gsplat_hip_pose_adjust_bwd(int64_t B, const float *camtoworlds, const float *deltas,
                                const float *v_out, float *v_deltas, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Appearance optimisation (ABI 38, new entries only; examples/utils.py
+ * AppearanceOptModule and simple_trainer.py app_opt, csrc/appearance.hip).
+ * Fixed dimensions: features[N,32], embeds[n_images,16], 16 SH bases of the
+ * module's degree 3, two hidden layers of width 64.  For camera c and
+ * Gaussian n:
+ *   x      = cat(embeds[embed_ids[c]], features[n], bases(normalize(means[n] - campos[c])))
+ *   colors = sigmoid(W3 relu(W2 relu(W1 x + b1) + b2) + b3 + base_colors[n])
+ * with the bases beyond (sh_degree + 1)^2 zero, the direction normalised as
+ * F.normalize (clamp 1e-12) and the basis of gsplat_hip_sh_fwd.  head[6] is a
+ * host array of the device pointers W1[64,64], b1[64], W2[64,64], b2[64],
+ * W3[3,64], b3[3] (torch Linear layout).  embeds or embed_ids NULL: the zero
+ * embedding (the reference's embed_ids=None); embed_ids[C] are device int64,
+ * clamped to [0, n_images).  masks u8[C,N] and radii i32[C,N] (visible where
+ * > 0) are both optional; a row either one hides is skipped: colour 0,
+ * gradient 0.  Both hidden layers are f32-input MFMA products, fp32 exact.
+ * features and v_features are read / written as float4 rows: both must be
+ * 16-B aligned (rows are 128 B, so the base pointer decides); every array is
+ * dense float32.
+ *
+ * _fwd writes colors[C,N,3].
+ * _bwd recomputes the activations from the same inputs and v_colors[C,N,3];
+ *   writes v_base_colors[N,3], v_features[N,32] and v_means[N,3] (summed over
+ *   cameras, every row written) and, per workgroup, one workspace row of
+ *   8515 + 16 C floats: the head's gradients in the order W1, b1, W2, b2, W3,
+ *   b3, then each camera's embedding gradient.  The workspace is
+ *   gsplat_hip_app_workspace_bytes of uninitialised memory; every row is
+ *   written.  No atomics: the same inputs give the same bits.
+ * _reduce_adam adds the workspace rows in a fixed order into grads[8515 + 16 C]
+ *   (always written).  With apply != 0 it then steps torch.optim.Adam in place:
+ *   the head (head[6], moments head_exp_avg / _sq [8515] in the flat order)
+ *   with lr, and -- embeds non-NULL -- the whole table [n_images,16] with
+ *   lr * embed_lr_mult and the L2 form g += embed_weight_decay * w; rows no
+ *   camera of the step shows get g = embed_weight_decay * w.  Factors: lr and
+ *   the 1-based step, or hyper_device f32[4] = (lr_head / (1 - beta1^t),
+ *   1 / sqrt(1 - beta2^t), lr_embed / (1 - beta1^t), unused).  skip_device
+ *   (may be NULL): non-zero = void step, no parameter or moment changes. */
+int64_t gsplat_hip_app_workspace_bytes(int64_t N, int C);
+int gsplat_hip_app_colors_fwd(int C, int64_t N, int sh_degree, const float *means,
+                              const float *campos, const float *features,
+                              const float *base_colors, const float *embeds,
+                              const int64_t *embed_ids, int n_images, const float *const *head,
+                              const uint8_t *masks, const int32_t *radii, float *colors,
+                              void *stream);
+int gsplat_hip_app_colors_bwd(int C, int64_t N, int sh_degree, const float *means,
+                              const float *campos, const float *features,
+                              const float *base_colors, const float *embeds,
+                              const int64_t *embed_ids, int n_images, const float *const *head,
+                              const uint8_t *masks, const int32_t *radii, const float *v_colors,
+                              float *v_base_colors, float *v_features, float *v_means,
+                              void *workspace, void *stream);
+int gsplat_hip_app_reduce_adam(int C, int64_t N, const void *workspace, float *grads, int apply,
+                               float *const *head, float *head_exp_avg, float *head_exp_avg_sq,
+                               float *embeds, const int64_t *embed_ids, int n_images,
+                               float *embed_exp_avg, float *embed_exp_avg_sq, float lr,
+                               float beta1, float beta2, float eps, float embed_lr_mult,
+                               float embed_weight_decay, int step, const float *hyper_device,
+                               const int32_t *skip_device, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
