@@ -8,6 +8,13 @@ identical kernel times).  Here the step is captured once with
 torch.cuda.CUDAGraph (HIP graphs on ROCm) and replayed: one replay, two
 small host->device copies and one device->host copy per step.
 
+The captured step is the eager step's own code: Trainer._run_step
+(train_step.py) issues both.  GraphStep._body passes it a StepInputs whose
+fields are views of the step's input block (BLOCK below), the sticky void
+flag, the isect capacity / status / report and the loss ring, where the
+eager step passes host values and views of its camera; everything else here
+is the capture, the block's host side and the overflow recovery.
+
 What makes the step capturable:
 * the sync-free intersection (`rasterization(_isect_capacity=...)`,
   gsplat_hip_isect_write_sorted_capped): isect arrays of a fixed capacity,
@@ -17,7 +24,7 @@ What makes the step capturable:
   (gsplat_hip_adam_step_dev, gsplat_hip_sh_colors_bwd_adam_dev; computed with
   the eager path's own arithmetic, losses.adam_factors), the camera's
   viewmat and K, and its index (the loss reads that camera's target image
-  in place, l1_ssim_loss(gt_index=...)) -- are one 512-B block.  The host
+  in place, l1_ssim_loss(gt_index=...)) -- are one 2-KB block.  The host
   writes it into a slot of a host-mapped ring; the graph's first kernel
   (the activations, gsplat_hip_activate_fwd_fetch) copies slot seq % RING
   into device memory and counts seq up, so a step needs no copy-engine
@@ -63,10 +70,8 @@ import numpy as np
 import torch
 
 from . import _lib, _wrapper
-from .losses import FusedAdam, adam_factors, l1_ssim_loss
-from .rendering import rasterization, rasterization_2dgs
+from .losses import FusedAdam, adam_factors
 from . import mcmc as _mcmc
-from .strategy import activate, update_state_
 
 
 class GraphCaptureError(RuntimeError):
@@ -91,18 +96,18 @@ def graphable(tr) -> bool:
     # (distributed.EMULATION, bench --gshard-emulate)
     from . import distributed as gdist
     rccl_ok = os.environ.get("GSPLAT_HIP_GRAPH_RCCL", "1") != "0"
-    gshard_ok = (getattr(tr, "gshard", False) and tr.world_size <= GraphStep.MAX_WORLD
+    gshard_ok = (tr.gshard and tr.world_size <= GraphStep.MAX_WORLD
                  and isinstance(tr.opt, FusedAdam) and (gdist.EMULATION is not None or rccl_ok))
     # per-camera data parallelism with the sharded optimizer (bench --dp-path):
     # its reduce-scatters / all-gathers inside the graph (none on a one-rank
     # group, distributed.ShardedAdam.solo)
     dp_ok = (tr.sharded and isinstance(tr.opt, gdist.ShardedAdam)
              and (tr.opt.solo or rccl_ok))
-    one = tr.world_size == 1 and not getattr(tr, "gshard", False) and not tr.sharded
+    one = tr.world_size == 1 and not tr.gshard and not tr.sharded
     # one rank: 3DGS or 2DGS (surfels, rasterization_2dgs with the sync-free isect)
     return (tr.fused and (tr.model == "3dgs" or (one and tr.model == "2dgs"))
             and (gshard_ok or dp_ok or (one and isinstance(tr.opt, FusedAdam)))
-            and not getattr(tr, "packed", False)
+            and not tr.packed
             and (st is None or (not getattr(st, "absgrad", False) and tr.radii2d is None))
             and torch.device(tr.device).type == "cuda")
 
@@ -162,6 +167,53 @@ def check_kernel_nodes_only(g, allow_d2d=False):
     return names
 
 
+SLOT = 2048  # bytes of a step's input block
+MAX_WORLD = 8  # cameras of a Gaussian-sharded step in the block
+
+# The input block of a captured step, (name, byte offset, dtype, count): the
+# host writes a block per step into a slot of a host-mapped ring (_fill), the
+# step's first kernel copies it into device memory (gsplat_hip_step_fetch,
+# which writes the ring slot into `slot`), and its launches read these fields
+# (the offsets are the kernels' too).
+BLOCK = (
+    # the Gaussians' Adam factors (lr / (1 - b1^t), 1 / sqrt(1 - b2^t)) per
+    # launched group in launch order, then the SH-Adam's three (Trainer._layout)
+    ("adam", 0, "float32", 56),
+    # the side optimizers' factors (train_step.SideOptimizer.name): the
+    # appearance module's, the bilateral grids', the pose table's
+    ("app", 224, "float32", 4),
+    ("bil", 240, "float32", 2),
+    ("pose", 248, "float32", 2),
+    ("cam", 256, "int64", 1),  # the rank's camera index
+    ("mcmc_step", 264, "int64", 1),  # MCMC: the step index and its noise scale
+    ("mcmc_scale", 272, "float32", 1),
+    ("viewmats", 512, "float32", 16 * MAX_WORLD),  # [W][16], W = the world's cameras
+    ("Ks", 1024, "float32", 9 * MAX_WORLD),  # [W][9]
+    ("c2w", 1536, "float32", 16),  # 2DGS: the camera-to-world matrix (its normals)
+    ("slot", SLOT - 8, "int64", 1),
+)
+_ITEM = {"float32": 4, "int64": 8}
+
+
+def _check_block():
+    """No two fields overlap, each is aligned and inside the block."""
+    end = 0
+    for name, off, dt, n in sorted(BLOCK, key=lambda f: f[1]):
+        assert off >= end and off % _ITEM[dt] == 0, f"step block: field {name} at {off}"
+        end = off + n * _ITEM[dt]
+    assert end <= SLOT, end
+
+
+_check_block()
+
+
+def block_views(buf, lib):
+    """{field: its typed view} of a SLOT-byte uint8 buffer: a torch tensor
+    (lib = torch) or a numpy array (lib = numpy)."""
+    return {name: buf[off:off + n * _ITEM[dt]].view(getattr(lib, dt))
+            for name, off, dt, n in BLOCK}
+
+
 class _Mapped:
     """Host-mapped, coherent memory (gsplat_hip_host_mapped_alloc): `np` for
     the host, `dev` (a pointer) for kernels.  Never freed: a captured graph
@@ -182,12 +234,9 @@ class GraphStep:
     """Trainer.step as HIP graph replays (see the module docstring)."""
 
     RING = 8  # host-mapped slots for the per-step input block and counts
-    SLOT = 2048  # bytes per input block
+    SLOT = SLOT
     LOSS_RING = 4096  # device slots of the returned per-step losses
-    MAX_WORLD = 8  # cameras of a Gaussian-sharded step in the block
-    BIL = 60  # floats [60, 62) of the block: the bilateral grids' Adam factors
-    POSE = 62  # floats [62, 64): the pose table's Adam factors (Trainer(pose_opt=True))
-    APP = 56  # floats [56, 60): the appearance module's Adam factors (Trainer(app_opt=True))
+    MAX_WORLD = MAX_WORLD
 
     def __init__(self, tr, capacity=None, headroom=1.25, lag=2):
         assert graphable(tr), "GraphStep: a fused 3DGS trainer (graph_step.graphable)"
@@ -197,17 +246,7 @@ class GraphStep:
         self.headroom = float(headroom)
         self.lag = int(lag)  # steps the host may run ahead of its overflow check
         self.capacity = None if capacity is None else int(capacity)
-        # device input of the graph: one 2-KB block per step -- f32 [0, 64)
-        # the Adam factors (the bilateral grids' at [BIL, BIL + 2)), i64 at
-        # byte 256 the rank's camera index, f32
-        # viewmats [W][16] at byte 512 and Ks [W][9] at
-        # byte 1024 (W = the world's cameras: 1, or the Gaussian-sharded job's
-        # ranks), the camera-to-world matrix f32 [16] at byte 1536 (2DGS: its
-        # normals), MCMC's step i64 / noise scale f32 at bytes 264 / 272,
-        # i64 at SLOT - 8 the ring slot (written by
-        # gsplat_hip_step_fetch)
-        self.n_groups = len(tr.params)
-        self.gshard = bool(getattr(tr, "gshard", False))
+        self.gshard = bool(tr.gshard)
         self.dp = bool(tr.sharded)  # per-camera data parallel, distributed.ShardedAdam
         self.W = tr.world_size if self.gshard else 1
         # the ranks agree on the overflow flag inside the graph (module docstring)
@@ -222,55 +261,33 @@ class GraphStep:
         self.cap_pg = None
         if self.vote and dist.get_backend() == "nccl":
             self.cap_pg = gdist.new_capture_group()
-        self.blk = torch.zeros(self.SLOT, dtype=torch.uint8, device=dev)
-        self.scal = self.blk[:256].view(torch.float32)
-        self.cam = self.blk[256:264].view(torch.int64)
-        self.vm_w = self.blk[512:512 + 64 * self.W].view(torch.float32).view(self.W, 4, 4)
-        self.K_w = self.blk[1024:1024 + 36 * self.W].view(torch.float32).view(self.W, 3, 3)
-        r = tr.rank if self.gshard else 0
-        self.vm, self.K = self.vm_w[r:r + 1], self.K_w[r:r + 1]  # this rank's camera
-        self.c2w = self.blk[1536:1536 + 64].view(torch.float32).view(1, 4, 4)
-        # MCMC: the step index (i64 at byte 264) and its noise scale (f32 at 272)
-        self.mstep = self.blk[264:272].view(torch.int64)
-        self.mscale = self.blk[272:276].view(torch.float32)
-        self.slot = self.blk[self.SLOT - 8:].view(torch.int64)
+        # device input of the graph: one block per step (BLOCK), and its fields
+        self.blk = torch.zeros(SLOT, dtype=torch.uint8, device=dev)
+        self.field = block_views(self.blk, torch)
+        # the largest launch plan (the sharded optimizer's: a shard launch and a
+        # remainder launch per group) and the SH-Adam's three fit the field
+        assert 4 * len(tr.params) + 3 <= self.field["adam"].numel(), len(tr.params)
+        self.vm_w = self.field["viewmats"][:16 * self.W].view(self.W, 4, 4)
+        self.K_w = self.field["Ks"][:9 * self.W].view(self.W, 3, 3)
         self.seq = torch.zeros(1, dtype=torch.int64, device=dev)  # steps fetched
         # the step's loss, written by the loss's own reduction launch into
         # slot (seq - 1) % LOSS_RING: step() returns that slot, no copy launch
         # after the replay (a 4-B device copy cost ~4 us of GPU time a step);
-        # a returned loss stays valid for LOSS_RING later steps
+        # a returned loss stays valid for LOSS_RING later steps.  Bypassed
+        # where the loss is a sum formed after the photometric launch: the
+        # regularisers, an active 2DGS geometry term (Trainer.geometry_terms_at,
+        # `terms`: the captured step's, part of the capture's key), the
+        # bilateral grid's tv, the depth term
         self.loss_ring = torch.zeros(self.LOSS_RING, dtype=torch.float32, device=dev)
-        self.ring_loss = not (getattr(tr, "opacity_reg", 0.0) > 0.0 or
-                              getattr(tr, "scale_reg", 0.0) > 0.0)
-        # 2DGS: the (normal_lambda, dist_lambda) of the captured step
-        # (Trainer.geometry_terms_at; part of the capture's key).  With a term
-        # active the loss is a sum formed after the photometric launch: the
-        # ring is bypassed, as with the regularisers
+        self.ring_loss = not (tr.opacity_reg > 0.0 or tr.scale_reg > 0.0
+                              or tr.bilateral_grid or tr.depth_loss)
         self.terms = (0.0, 0.0)
-        # the bilateral grid (Trainer(bilateral_grid=True)): the slice between
-        # the render and the loss and 10 x tv added after it (ring bypassed),
-        # the grids' Adam factors at floats [BIL, BIL + 2) of the block
-        self.bil = bool(getattr(tr, "bilateral_grid", False))
-        # sparse depth supervision (Trainer(depth_loss=True)): the RGB+D render,
-        # the photometric loss and the depth term of the block's camera as
-        # one node (Trainer.depth_losses), their sum formed after it (ring
-        # bypassed)
-        self.depth = bool(getattr(tr, "depth_loss", False))
-        self.ring_now = self.ring_loss and not self.bil and not self.depth
-        # camera pose optimisation (Trainer(pose_opt=True) / pose_noise): the
-        # step's view matrix made from the block's by pose.pose_apply right
-        # after the fetch, the pose Adam (its factors at floats [POSE, POSE + 2))
-        # a launch after the other updates
-        self.pose = bool(getattr(tr, "pose_opt", False))
-        self.pose_any = bool(getattr(tr, "pose_active", False))
-        # appearance optimisation (Trainer(app_opt=True)): the colours from the
-        # appearance MLP after the projection, the embedding row chosen by the
-        # block's camera index, the module's two Adam optimizers (factors at
-        # floats [APP, APP + 4)) a launch after the other updates
-        self.app = bool(getattr(tr, "app_opt", False))
+        self.ring_now = self.ring_loss
         self._warmed = set()  # the active-term sets a warm-up step has run for
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)  # sticky overflow flag
-        self.ring_in = _Mapped(self.RING * self.SLOT)
+        self.ring_in = _Mapped(self.RING * SLOT)
+        self._host = [block_views(self.ring_in.np[k * SLOT:(k + 1) * SLOT], np)
+                      for k in range(self.RING)]  # the ring slots' fields
         self.ring_out = _Mapped(self.RING * 4 * 8)
         self._out = self.ring_out.np.view(np.int64).reshape(self.RING, 4)
         self._slot_ev = [None] * self.RING
@@ -293,174 +310,41 @@ class GraphStep:
         self.failed = None
 
     # ------------------------------------------------------------------ body
-    def _layout(self):
-        """(groups of the Adam launches in launch order, offset of the SH-Adam
-        factors): the device-side factors are laid out in that order."""
-        if self.dp:
-            idx = [i for sel in self.tr.opt.launch_plan() for i in sel]
-            return idx, 2 * len(idx)
-        names = list(self.tr.params)
-        sh = {names.index(k) for k in ("sh0", "shN") if k in names}
-        idx = [i for i in range(self.n_groups) if not (self.tr.sh_adam_in_bwd and i in sh)]
-        return idx, 2 * len(idx)
-
     def _body(self, deg, stats=True):
-        tr = self.tr
-        p = tr.params
-        names = list(p)
-        idx, sh_off = self._layout()
-        fa = None
-        if tr.sh_adam_in_bwd:
-            o = tr.opt
-            i0, i1 = names.index("sh0"), names.index("shN")
-            fa = _wrapper.ShAdamInBackward(
-                p["sh0"].data, p["shN"].data, o.exp_avg[i0], o.exp_avg_sq[i0], o.exp_avg[i1],
-                o.exp_avg_sq[i1], o.lrs[i0], o.lrs[i1], o.betas, o.eps, 1,
-                hyper=self.scal[sh_off:sh_off + 3], skip=self.status)
-        ga = None
-        if getattr(tr, "geom_in_proj", False):
-            # the geometry groups' factors are the first launch groups' (_fill):
-            # (ss, ib) of means, scales, quats, opacities at [0, 8); the SH
-            # groups follow when their update is not fused into the SH backward
-            assert [names[i] for i in idx][:len(tr.GEOM)] == list(tr.GEOM), (idx, names)
-            ga = tr.geom_adam_in_backward(1, hyper=self.scal[:2 * len(idx)], skip=self.status)
-            if self.pose:
-                ga.pose_ws = tr._pose_workspace()
-        fusion = _wrapper.StepFusion(sh_adam=fa, geom=tr.geom_fuse, geom_adam=ga) \
-            if (fa is not None or tr.geom_fuse) else None
-        # the first launch also fetches this step's input block (the ring slot)
-        scales, opac = activate(p["scales"], p["opacities"], fusion,
-                                fetch=(self.ring_in.dev, self.SLOT, self.RING, self.seq, self.blk))
-        vm = self.vm
-        if self.pose_any:  # Trainer._eager_step's launch (a), camera and index from the block
-            vm = tr._pose_viewmat(self.vm, self.cam)
-        dkw = {}
-        if self.gshard:  # the world's cameras from the block, shard sizes fixed per capture
-            dkw = dict(distributed=True, _world_cameras=(self.vm_w, self.K_w),
-                       _world_counts=tr._n_world)
-        grad_box = {}
-        terms = self.terms
-        if tr.model == "2dgs" and any(terms):
-            # Trainer.render(geometry=terms)'s call, with the sync-free isect
-            rc, ra, rn, _, rd, _, meta = rasterization_2dgs(
-                p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), self.vm, self.K,
-                tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
-                far_plane=1e10, render_mode="RGB+D", distloss=bool(terms[1]), _fusion=fusion,
-                _isect_capacity=self.capacity, _isect_status=self.status,
-                _isect_report=(self.ring_out.dev, self.slot), _camtoworlds=self.c2w,
-                _geometry=True)
-            colors = meta["_rgbd"] = rc
-            meta["_geometry"] = (rn, ra, rd)
-        elif tr.model == "2dgs":  # Trainer.render's call, with the sync-free isect
-            rc, _, _, _, _, _, meta = rasterization_2dgs(
-                p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), self.vm, self.K,
-                tr.width, tr.height, sh_degree=deg, packed=False, near_plane=0.01,
-                far_plane=1e10, render_mode="RGB+D", _fusion=fusion,
-                _isect_capacity=self.capacity, _isect_status=self.status,
-                _isect_report=(self.ring_out.dev, self.slot), _camtoworlds=self.c2w,
-                _colors_only=True)
-            colors = rc  # the loss reads the colour channels in place (_channels=3)
-            # the densification input is a leaf: its .grad after the backward
-            # (a hook keeping a reference would make AccumulateGrad clone the
-            # gradient -- a memcpy node in the graph)
-        else:
-            coeffs, deg_r = None, deg
-            if self.app:  # Trainer.render's colours, the embedding row chosen on the device
-                coeffs, deg_r = p["colors"], None
-                dkw["_app"] = tr._app_colors(vm, deg, self.cam, fusion)
-            else:
-                coeffs = (p["sh0"], p["shN"])
-            with _wrapper.fwd_split(getattr(tr, "split_div", None),
-                                    getattr(tr, "split_threshold", None)):
-                colors, alphas, meta = rasterization(
-                    p["means"], p["quats"], scales, opac, coeffs, vm, self.K,
-                    tr.width, tr.height, sh_degree=deg_r, packed=False, near_plane=0.01,
-                    far_plane=1e10, radius_clip=0.0,
-                    rasterize_mode=getattr(tr, "rasterize_mode", "classic"),
-                    render_mode="RGB+D" if self.depth else "RGB", _fusion=fusion,
-                    _isect_capacity=self.capacity, _isect_status=self.status,
-                    _isect_report=(self.ring_out.dev, self.slot), _isect_ids=False, **dkw)
-            meta["means2d"].register_hook(lambda g: grad_box.__setitem__("g", g))
-        tv = None
-        if self.depth:
-            rgbd = colors
-        elif self.bil:  # Trainer._eager_step's slice, the grid chosen on the device
-            from .bilagrid import _slice_tv
-            colors, tv = _slice_tv(tr.bil_grids, colors, self.cam, tr.BIL_TV_WEIGHT)
-        vote = None
-        if self.vote:  # the ranks' overflow flags, agreed beside the loss kernels
-            import torch.distributed as dist
-            from . import distributed as gdist
-            vote = dist.all_reduce(self.status, op=dist.ReduceOp.MAX, async_op=True,
-                                   group=gdist.current_capture_group())
-        if self.depth:  # Trainer._eager_step's losses, image and target chosen on the device
-            photo, term, tv = tr.depth_losses(rgbd, alphas, tr.targets, self.cam,
-                                              gt_index=self.cam)
-            loss = photo + term
-        else:
-            loss = l1_ssim_loss(
-                colors, tr.targets, tr.ssim_lambda, gt_index=self.cam,
-                _out_ring=(self.loss_ring, self.seq) if self.ring_now else None,
-                _channels=3 if tr.model == "2dgs" else None)
-        if any(terms):
-            loss = loss + tr.geometry_loss(meta, self.K, terms)
-        if tv is not None:
-            loss = loss + tv
-        loss = tr._regularise(loss)
-        if vote is not None:
-            vote.wait()
-            _lib.call("gsplat_hip_status_to_ring", self.status.data_ptr(), self.ring_out.dev,
-                      self.slot.data_ptr(), _wrapper._stream())
-        from . import losses as _losses
-        tr._sh_ready = 0  # the sharded optimizer's SH reduce-scatter hook
+        """Trainer._run_step on the block's views, the void flag and the rings;
+        MCMC's position noise is a launch of the captured step."""
+        from .train_step import StepInputs
+        tr, f = self.tr, self.field
+        isect = dict(_isect_capacity=self.capacity, _isect_status=self.status,
+                     _isect_report=(self.ring_out.dev, f["slot"]))
+        if tr.model == "3dgs":
+            isect["_isect_ids"] = False
+        s = StepInputs(
+            deg=deg, terms=self.terms, stats=stats, viewmats=self.vm_w, Ks=self.K_w,
+            cam=f["cam"], targets=tr.targets, gt_index=f["cam"], c2w=f["c2w"].view(1, 4, 4),
+            # the first launch also fetches this step's input block (the ring slot)
+            fetch=(self.ring_in.dev, SLOT, self.RING, self.seq, self.blk), isect=isect,
+            void=self.status, hyper=f["adam"],
+            side_hyper={so.name: f[so.name] for so in tr.side_opts},
+            loss_ring=(self.loss_ring, self.seq) if self.ring_now else None,
+            vote=self.vote, capturing=self.dp)
         if self.dp:  # its collectives in order on this stream (ShardedAdam.capturing)
             tr.opt.capturing = True
         try:
-            torch.autograd.backward(loss, _losses.ONE_GRAD)
-            if tr.model == "2dgs" and meta["gradient_2dgs"].grad is not None:
-                grad_box["g"] = meta["gradient_2dgs"].grad
-            if stats and "g" in grad_box:  # DefaultStrategy statistics (until refine_stop_iter)
-                update_state_(tr.grad2d, tr.count, grad_box["g"], meta["radii"], meta["width"],
-                              meta["height"], meta["n_cameras"], skip=self.status)
-            if self.dp:  # reduce-scatter, Adam on this rank's rows, all-gather: all inside
-                assert not tr._sh_skip(fusion)
-                tr.opt.step(defer_gather=False, xform=tr._geom_xform(fusion),
-                            hyper=self.scal[:sh_off], void=self.status)
-            else:
-                skip = tr._sh_skip(fusion)
-                launched = tuple(i for i in range(self.n_groups) if i not in skip)
-                # the launched groups are the launch plan's tail (the geometry
-                # groups, its head, may have been updated by the projection
-                # backward): their factors start at that offset
-                assert launched == tuple(idx[len(idx) - len(launched):]), (skip, idx)
-                off = 2 * (len(idx) - len(launched))
-                tr.opt.step(skip=skip, xform=tr._geom_xform(fusion),
-                            hyper=self.scal[off:sh_off], void=self.status)
+            loss, meta = tr._run_step(s)
         finally:
             # (also when the body raises: later eager steps use the optimizer's
             # own streams and communicators again)
             if self.dp:
                 tr.opt.capturing = False
-        tr.opt.zero_grad(set_to_none=True)
-        if self.bil:
-            tr.bil_opt.step(hyper=self.scal[self.BIL:self.BIL + 2], void=self.status)
-            tr.bil_opt.zero_grad()
-        if self.pose:  # Trainer._pose_step, factors and void flag on the device
-            from .pose import pose_bwd_adam
-            assert ga is not None and ga.applied, "pose_opt: the geometry Adam in the backward"
-            pose_bwd_adam(tr._pose_ws, p["means"].shape[0], self.vm, self.cam, tr.pose_embeds,
-                          tr._pose_m, tr._pose_v, 0.0, tr.pose_opt_reg, 1,
-                          noise=tr.pose_noise_table, hyper=self.scal[self.POSE:self.POSE + 2],
-                          skip=self.status)
-        if self.app:  # Trainer._app_step, factors and void flag on the device
-            tr._app_step(self.cam, hyper=self.scal[self.APP:self.APP + 4], skip=self.status)
-        if getattr(tr, "mcmc", False):
+        if tr.mcmc:
             # MCMCStrategy's position noise after the update (Trainer.mcmc_noise):
             # the step and its scale from the block (scale 0 on refine steps,
             # whose noise follows the eager refine), nothing on a void step
+            p = tr.params
             _mcmc.inject_noise({k: p[k].data for k in ("means", "quats", "scales", "opacities")},
-                               0.0, seed=tr._noise_seed, step_dev=self.mstep,
-                               scaler_dev=self.mscale, skip=self.status)
+                               0.0, seed=tr._noise_seed, step_dev=f["mcmc_step"],
+                               scaler_dev=f["mcmc_scale"], skip=self.status)
         return loss, meta["isect_counts"]
 
     def _capture(self, deg, stats=True):
@@ -497,22 +381,19 @@ class GraphStep:
 
     def _capture_impl(self, deg, stats=True):
         tr = self.tr
-        from . import losses as _losses
-        if _losses.ONE_GRAD is None or _losses.ONE_GRAD.device != self.dev:
-            _losses.ONE_GRAD = torch.ones((), device=self.dev)
+        from .train_step import _one_grad
+        _one_grad(self.dev)  # the backward's seed, made outside the capture
         if self.capacity is None:
             self.capacity = self._probe_capacity(deg)
         timers = _wrapper._timers
         _wrapper._timers = None  # no timing events inside the graph
         if self.dp:
             tr.opt.wait()  # an eager step's deferred all-gathers
-        if self.pose:
-            tr._pose_workspace()  # sized for the Gaussians, allocated outside the capture
-        if self.app:
-            tr._app_workspace()  # likewise
+        for so in tr.side_opts:
+            if so.workspace is not None:
+                so.workspace()  # sized for the Gaussians, allocated outside the capture
         torch.cuda.synchronize(self.dev)
-        self.ring_now = (self.ring_loss and not any(self.terms) and not self.bil
-                         and not self.depth)
+        self.ring_now = self.ring_loss and not any(self.terms)
         try:
             # warm-up on a side stream (torch's capture recipe) as a VOID
             # step: the flag makes every state update a no-op.  Only before
@@ -590,9 +471,9 @@ class GraphStep:
         lrs = list(o.lrs)
         if tr.max_steps:  # means ExponentialLR (Trainer.step sets it before Adam)
             lrs[0] = tr.lrs[0] * (0.01 ** (1.0 / tr.max_steps)) ** it
-        idx, sh_off = self._layout()
-        b = self.ring_in.np[slot * self.SLOT:(slot + 1) * self.SLOT]
-        f = b[:256].view(np.float32)
+        idx, sh_off = tr._layout()
+        h = self._host[slot]
+        f = h["adam"]
         fac = adam_factors([lrs[i] for i in idx], o.betas, step)
         for k, (ss, ib) in enumerate(fac):
             f[2 * k], f[2 * k + 1] = ss, ib
@@ -601,32 +482,19 @@ class GraphStep:
             (s0, ib), (sr, _) = adam_factors([lrs[names.index("sh0")], lrs[names.index("shN")]],
                                              o.betas, step)
             f[sh_off:sh_off + 3] = (s0, sr, ib)
-        if self.bil:  # the grids' Adam: its own betas, the chained schedule's lr
-            from .bilagrid import bilagrid_lr
-            bo = tr.bil_opt
-            bo.lrs[0] = bilagrid_lr(it, tr.max_steps, tr.bil_lr)
-            f[self.BIL], f[self.BIL + 1] = adam_factors(bo.lrs, bo.betas, bo.step_count + 1)[0]
-        if self.pose:
-            from .pose import BETAS
-            f[self.POSE], f[self.POSE + 1] = adam_factors([tr.pose_lr_at(it)], BETAS,
-                                                          tr.pose_step_count + 1)[0]
-        if self.app:  # torch's Adam for the head (lr) and the embedding table (10 x lr)
-            from .appearance import BETAS as APP_BETAS, EMBED_LR_MULT
-            (sh_, ib_), (se_, _) = adam_factors([tr.app_lr, tr.app_lr * EMBED_LR_MULT],
-                                                APP_BETAS, tr.app_step_count + 1)
-            f[self.APP:self.APP + 4] = (sh_, ib_, se_, 0.0)
+        for so in tr.side_opts:  # each with its own betas and schedule
+            h[so.name][:] = so.factors(it)
         ci = tr.camera_index(it)
         n = len(self._vm_host)
         world_ci = [(ci - tr.rank + r) % n for r in range(self.W)] if self.gshard else [ci]
-        b[512:512 + 64 * self.W].view(np.float32)[:] = self._vm_host[world_ci].reshape(-1)
-        b[1024:1024 + 36 * self.W].view(np.float32)[:] = self._K_host[world_ci].reshape(-1)
-        b[256:264].view(np.int64)[0] = ci
-        if getattr(tr, "mcmc", False):
-            b[264:272].view(np.int64)[0] = it
-            b[272:276].view(np.float32)[0] = \
-                0.0 if tr.strategy.is_refine_step(it) else tr.mcmc_scaler(it)
+        h["viewmats"][:16 * self.W] = self._vm_host[world_ci].reshape(-1)
+        h["Ks"][:9 * self.W] = self._K_host[world_ci].reshape(-1)
+        h["cam"][0] = ci
+        if tr.mcmc:
+            h["mcmc_step"][0] = it
+            h["mcmc_scale"][0] = 0.0 if tr.strategy.is_refine_step(it) else tr.mcmc_scaler(it)
         if tr.model == "2dgs":  # rasterization_2dgs's torch.linalg.inv(viewmats), on the host
-            b[1536:1536 + 64].view(np.float32)[:] = np.linalg.inv(
+            h["c2w"][:] = np.linalg.inv(
                 self._vm_host[ci].astype(np.float64)).astype(np.float32).reshape(-1)
         if tr.max_steps:
             tr._set_means_lr(lrs[0])
@@ -639,13 +507,13 @@ class GraphStep:
         whether the bilateral grid is sliced and whether the camera pose is
         adjusted / optimised."""
         tr = self.tr
-        return (deg, tr.params["means"].shape[0], getattr(tr, "_param_gen", 0), stats,
-                self.terms if terms is None else tuple(terms), self.bil,
-                (self.pose_any, self.pose))
+        return (deg, tr.params["means"].shape[0], tr._param_gen, stats,
+                self.terms if terms is None else tuple(terms), tr.bilateral_grid,
+                (tr.pose_active, tr.pose_opt))
 
     def _stats_at(self, it):
         st = self.tr.strategy
-        if getattr(self.tr, "mcmc", False):
+        if self.tr.mcmc:
             return False  # MCMCStrategy keeps no statistics
         return st is None or it < st.refine_stop_iter
 
@@ -679,6 +547,13 @@ class GraphStep:
             raise GraphCaptureError(self.failed)
         return self._issue(it)
 
+    def _advance(self, n):
+        """The step counts of every Adam of the step (a replay's updates read
+        their factors from the block: the counts are kept here)."""
+        self.tr.opt.step_count += n
+        for so in self.tr.side_opts:
+            so.advance(n)
+
     def _issue(self, it, ret=None):
         """Replay step `it` as the `issued`-th step; returns its loss: the
         loss-ring slot `issued % LOSS_RING` (written by the loss launch), or,
@@ -694,13 +569,7 @@ class GraphStep:
         t0 = time.perf_counter()
         self._fill(it, slot)
         self.graph.replay()
-        self.tr.opt.step_count += 1
-        if self.bil:
-            self.tr.bil_opt.step_count += 1
-        if self.pose:
-            self.tr.pose_step_count += 1
-        if self.app:
-            self.tr.app_step_count += 1
+        self._advance(1)
         if self.ring_now:
             ret = self.loss_ring[k % self.LOSS_RING]
         elif ret is None:
@@ -746,13 +615,7 @@ class GraphStep:
         for _, slot, _, _, _ in self.pending:
             self.max_isects = max(self.max_isects, int(self._out[slot][3]))
         self.pending.clear()
-        tr.opt.step_count -= len(redo)  # their Adam steps did not happen
-        if self.bil:
-            tr.bil_opt.step_count -= len(redo)
-        if self.pose:
-            tr.pose_step_count -= len(redo)
-        if self.app:
-            tr.app_step_count -= len(redo)
+        self._advance(-len(redo))  # their Adam steps did not happen
         # (a rank voided by another's overflow keeps at least its capacity)
         self.capacity = max(self.capacity or 0,
                             int(math.ceil(self.max_isects * self.headroom)) + 1)
@@ -771,7 +634,7 @@ class GraphStep:
             self.graph, self.key = None, None
             for it, _, ret in redo:
                 loss = tr._eager_step(it)
-                if getattr(tr, "mcmc", False) and not tr.strategy.is_refine_step(it):
+                if tr.mcmc and not tr.strategy.is_refine_step(it):
                     tr.mcmc_noise(it)  # the replay's noise (a refine step's follows its refine)
                 if ret is not None:
                     ret.copy_(loss.detach().reshape(ret.shape))

@@ -7,6 +7,14 @@ config (sh_degree 3, packed=False, classic rasterize mode, batch 1):
   statistics (gsplat/strategy/default.py:213-262) -> Adam on every parameter
   group with the trainer's learning rates and batch scaling (:235-277).
 
+Trainer._run_step is that step, and the only place that issues one: the
+eager step (_eager_step) and the graph-replayed step (graph_step.GraphStep)
+call it with a StepInputs record saying where the step's inputs live -- host
+values and views of the step's camera, or views of the captured step's input
+block, its void flag and its rings.  The Adam optimizers beside the
+Gaussians' (the bilateral grids', the pose table's, the appearance module's)
+are one ordered list, Trainer.side_opts.
+
 model="2dgs" runs examples/simple_trainer_2dgs.py's default step instead:
 rasterization_2dgs(render_mode="RGB+D") (simple_trainer_2dgs.py:549-563), the
 same loss on the RGB channels (:590-594), and the strategy statistics from
@@ -94,7 +102,7 @@ camera each step:
 import dataclasses
 import math
 import os
-from typing import Dict, Optional, Union
+from typing import Callable, Optional, Union
 
 import numpy as np
 import torch
@@ -104,8 +112,8 @@ from . import densify
 from .densify import DefaultStrategyConfig
 from . import mcmc as _mcmc
 from .mcmc import MCMCStrategyConfig
-from .losses import FusedAdam, l1_ssim_loss, ssim_and_l1
-from . import _wrapper
+from .losses import FusedAdam, adam_factors, l1_ssim_loss, ssim_and_l1
+from . import _lib, _wrapper
 from .rendering import rasterization, rasterization_2dgs
 from .strategy import activate, update_state_
 
@@ -204,10 +212,112 @@ def _mean(x: torch.Tensor) -> torch.Tensor:
     return s / n
 
 
+@dataclasses.dataclass
+class StepInputs:
+    """Where one training step's inputs live (Trainer._run_step).  The eager
+    step fills it from host values and views of its camera `ci`, everything
+    device-side None; the captured step (graph_step.GraphStep) from the views
+    of its input block, its void flag and its rings."""
+    deg: int  # SH degree
+    terms: tuple  # 2DGS (normal_lambda, dist_lambda), geometry_terms_at
+    stats: bool  # accumulate the DefaultStrategy statistics
+    viewmats: torch.Tensor  # [W,4,4], W = 1 or the Gaussian-sharded world (rank order)
+    Ks: torch.Tensor  # [W,3,3]
+    cam: torch.Tensor  # device int64 [1]: the step's image
+    targets: torch.Tensor  # the image's target [1,H,W,3], or all of them with gt_index
+    gt_index: Optional[torch.Tensor] = None
+    c2w: Optional[torch.Tensor] = None  # 2DGS: the camera-to-world [1,4,4]
+    it: Optional[int] = None  # host factors: the step index their schedules read
+    fetch: Optional[tuple] = None  # activate's: the first launch fetches the input block
+    isect: dict = dataclasses.field(default_factory=dict)  # the sync-free isect's keywords
+    void: Optional[torch.Tensor] = None  # device i32 flag: every state update reads it
+    hyper: Optional[torch.Tensor] = None  # the Gaussians' Adam factors (Trainer._layout order)
+    side_hyper: dict = dataclasses.field(default_factory=dict)  # SideOptimizer.name -> factors
+    loss_ring: Optional[tuple] = None  # l1_ssim_loss's _out_ring
+    vote: bool = False  # several ranks: agree on the void flag beside the loss kernels
+    capturing: bool = False  # sharded optimizer: collectives in order, no deferred gather
+
+
+@dataclasses.dataclass
+class SideOptimizer:
+    """An Adam beside the Gaussians' (the bilateral grids', the pose table's,
+    the appearance module's), launched after it in Trainer.side_opts' order.
+    `counter`: (object, attribute) of its step count; `factors(it)`: the floats
+    of its slot `name` of the captured step's block for the step after that
+    count; `launch(inputs, hyper)`: with hyper None the host's factors, counting
+    the step itself (as FusedAdam.step does), else the slot's, the count being
+    the caller's business; `workspace`: allocated outside a capture."""
+    name: str
+    counter: tuple
+    factors: Callable
+    launch: Callable
+    workspace: Optional[Callable] = None
+
+    def advance(self, n: int):
+        obj, attr = self.counter
+        setattr(obj, attr, getattr(obj, attr) + n)
+
+
+# Trainer options of the one-GPU dense trainer, and the companions (Trainer.
+# __init__'s `asked`) each is refused with
+_MANY = ("gaussian_shard", "sharded_optimizer", "world_size")
+_SPARSE = ("packed", "sparse_grad", "visible_adam")
+# option -> (the trainer it runs in, the companions it is refused with)
+_REFUSALS = {
+    "app_opt": ("the one-GPU dense fused 3DGS trainer only",
+                ("pose_opt", "pose_noise", "model='2dgs'") + _SPARSE + _MANY + ("fused=False",)),
+    "depth_loss": ("the one-GPU dense fused 3DGS trainer only",
+                   ("model='2dgs'",) + _SPARSE + _MANY + ("fused=False",)),
+    "pose": ("the one-GPU dense fused 3DGS trainer with the geometry Adam in the projection "
+             "backward only",
+             ("model='2dgs'",) + _SPARSE + ("antialiased", "opacity_reg", "scale_reg") + _MANY
+             + ("fused=False", "GSPLAT_HIP_GEOM_FUSE=0", "GSPLAT_HIP_GEOM_IN_PROJ=0")),
+    "bilateral_grid": ("the one-GPU dense 3DGS trainer only", ("model='2dgs'",) + _SPARSE + _MANY),
+    "normal_loss / dist_loss": ("the one-GPU dense 2DGS trainer only",
+                                ("packed", "sparse_grad") + _MANY),
+}
+
+
+def _refuse(option, asked, name=None):
+    """NotImplementedError naming `option` (as `name`) and every companion of
+    its _REFUSALS row that the constructor's arguments ask for (`asked`)."""
+    scope, companions = _REFUSALS[option]
+    off = [c for c in companions if asked[c]]
+    if off:
+        raise NotImplementedError(f"{name or option}: {scope}; not with {', '.join(off)}")
+
+
+def _one_grad(device):
+    """The constant 1.0 seed of the fused loss's backward (no fill launch; the
+    backward recognises it and skips its scaling launch), made outside a
+    capture."""
+    from . import losses as _losses
+    if _losses.ONE_GRAD is None or _losses.ONE_GRAD.device != device:
+        _losses.ONE_GRAD = torch.ones((), device=device)
+    return _losses.ONE_GRAD
+
+
 class Trainer:
     """Holds the Gaussian parameters, Adam state and strategy statistics."""
 
     BIL_TV_WEIGHT = 10.0  # simple_trainer.py:664: loss += 10 * tv
+
+    # every option flag and lazily set attribute has its default here, so a
+    # Trainer that did not go through __init__ (a test's skeleton) reads them too
+    model = "3dgs"
+    bilateral_grid = pose_opt = depth_loss = app_opt = False
+    pose_noise = 0.0
+    normal_loss = dist_loss = False
+    gshard = packed = sparse_grad = visible_adam = mcmc = False
+    sh_adam_in_bwd = geom_fuse = geom_in_proj = geom_applied = False
+    rasterize_mode = "classic"
+    opacity_reg = scale_reg = 0.0
+    dp_emulate_world = _sh_pg = None
+    side_opts = ()
+    _graph = graph_fallback = None
+    _param_gen = 0
+    split_div = split_threshold = None
+    _split_tuned = False
 
     LRS = {"means": 1.6e-4, "scales": 5e-3, "quats": 1e-3, "opacities": 5e-2,
            "sh0": 2.5e-3, "shN": 2.5e-3 / 20, "features": 2.5e-3, "colors": 2.5e-3}
@@ -233,25 +343,26 @@ class Trainer:
                  app_opt_lr: float = 1e-3, app_opt_reg: float = 1e-6):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # the options of the one-GPU dense trainer, each refused with what it
+        # does not run with (_REFUSALS) before any device work
+        env = os.environ.get
+        asked = {
+            "pose_opt": pose_opt, "pose_noise": float(pose_noise) != 0.0,
+            "model='2dgs'": model != "3dgs", "packed": packed, "sparse_grad": sparse_grad,
+            "visible_adam": visible_adam, "antialiased": antialiased,
+            "opacity_reg": float(opacity_reg) != 0.0, "scale_reg": float(scale_reg) != 0.0,
+            "gaussian_shard": gaussian_shard, "sharded_optimizer": sharded_optimizer,
+            "world_size": world_size != 1, "fused=False": not fused,
+            "GSPLAT_HIP_GEOM_FUSE=0": env("GSPLAT_HIP_GEOM_FUSE", "1") == "0",
+            "GSPLAT_HIP_GEOM_IN_PROJ=0": env("GSPLAT_HIP_GEOM_IN_PROJ", "1") == "0"}
         # simple_trainer.py app_opt / app_embed_dim / app_opt_lr / app_opt_reg
         # (:243-254, 389-410): the colours from the appearance MLP over
         # `features` [N,32], a per-image embedding and the view direction's SH
-        # bases, plus the logits `colors` (appearance.py); the one-GPU dense
-        # fused 3DGS trainer only, refused before any device work
+        # bases, plus the logits `colors` (appearance.py)
         self.app_opt = bool(app_opt)
         self.app_opt_reg = float(app_opt_reg)
         if self.app_opt:
-            off = [name for name, on in (
-                ("pose_opt", bool(pose_opt)), ("pose_noise", float(pose_noise) != 0.0),
-                ("model='2dgs'", model != "3dgs"), ("packed", packed),
-                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
-                ("gaussian_shard", gaussian_shard),
-                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
-                ("fused=False", not fused)) if on]
-            if off:
-                raise NotImplementedError(
-                    "app_opt: the one-GPU dense fused 3DGS trainer only; not with "
-                    f"{', '.join(off)}")
+            _refuse("app_opt", asked)
             if int(app_embed_dim) != 16:
                 raise ValueError("app_opt: app_embed_dim is fixed at 16 (the kernels' layout), "
                                  f"got {app_embed_dim!r}")
@@ -261,19 +372,10 @@ class Trainer:
         # simple_trainer.py depth_loss / depth_lambda (:163-165, 647-665): the
         # disparity L1 at each image's projected SfM points (depth_loss.py),
         # added to the loss times depth_lambda * scene_scale; the step then
-        # renders RGB+D.  The one-GPU dense fused 3DGS trainer only
+        # renders RGB+D
         self.depth_loss, self.depth_lambda = bool(depth_loss), float(depth_lambda)
         if self.depth_loss:
-            off = [name for name, on in (
-                ("model='2dgs'", model != "3dgs"), ("packed", packed),
-                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
-                ("gaussian_shard", gaussian_shard),
-                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
-                ("fused=False", not fused)) if on]
-            if off:
-                raise NotImplementedError(
-                    "depth_loss: the one-GPU dense fused 3DGS trainer only; not with "
-                    f"{', '.join(off)}")
+            _refuse("depth_loss", asked)
             if depth_points is None:
                 raise ValueError("depth_loss: depth_points, one (points [M, 2], depths [M]) per "
                                  "training image, is required")
@@ -288,49 +390,26 @@ class Trainer:
         self.pose_opt_reg = float(pose_opt_reg)
         if self.pose_noise < 0.0:
             raise ValueError(f"pose_noise: a standard deviation >= 0, got {pose_noise!r}")
-        if self.pose_opt or self.pose_noise > 0.0:
-            what = "pose_opt" if self.pose_opt else "pose_noise"
-            off = [name for name, on in (
-                ("model='2dgs'", model != "3dgs"), ("packed", packed),
-                ("sparse_grad", sparse_grad), ("visible_adam", visible_adam),
-                ("antialiased", antialiased), ("opacity_reg", float(opacity_reg) != 0.0),
-                ("scale_reg", float(scale_reg) != 0.0), ("gaussian_shard", gaussian_shard),
-                ("sharded_optimizer", bool(sharded_optimizer)), ("world_size", world_size != 1),
-                ("fused=False", not fused),
-                ("GSPLAT_HIP_GEOM_FUSE=0", os.environ.get("GSPLAT_HIP_GEOM_FUSE", "1") == "0"),
-                ("GSPLAT_HIP_GEOM_IN_PROJ=0",
-                 os.environ.get("GSPLAT_HIP_GEOM_IN_PROJ", "1") == "0")) if on]
-            if off:
-                raise NotImplementedError(
-                    f"{what}: the one-GPU dense fused 3DGS trainer with the geometry Adam in "
-                    f"the projection backward only; not with {', '.join(off)}")
-
+        if self.pose_active:
+            _refuse("pose", asked, "pose_opt" if self.pose_opt else "pose_noise")
         # simple_trainer.py use_bilateral_grid / bilateral_grid_shape: one grid
         # of affine colour transforms per training image, sliced between the
-        # render and the loss (bilagrid.py); the one-GPU dense 3DGS trainer only
+        # render and the loss (bilagrid.py)
         self.bilateral_grid = bool(bilateral_grid)
         self.bilateral_grid_shape = tuple(int(v) for v in bilateral_grid_shape)
         if self.bilateral_grid:
-            if (model != "3dgs" or packed or sparse_grad or visible_adam or gaussian_shard
-                    or sharded_optimizer or world_size != 1):
-                raise NotImplementedError(
-                    "bilateral_grid: the one-GPU dense 3DGS trainer only (not model='2dgs', "
-                    "packed, sparse_grad, visible_adam, Gaussian-sharded, sharded-optimizer or "
-                    "multi-rank trainers)")
+            _refuse("bilateral_grid", asked)
             if len(self.bilateral_grid_shape) != 3 or min(self.bilateral_grid_shape) < 2:
                 raise ValueError("bilateral_grid_shape: (X, Y, W), each >= 2, got "
                                  f"{bilateral_grid_shape!r}")
         # simple_trainer_2dgs.py:149-160, 611-632: the normal-consistency and
         # depth-distortion terms, each from its start iteration on (step >
-        # start_iter); the one-GPU 2DGS trainer only
+        # start_iter)
         self.normal_loss, self.dist_loss = bool(normal_loss), bool(dist_loss)
         self.normal_lambda, self.dist_lambda = float(normal_lambda), float(dist_lambda)
         self.normal_start_iter, self.dist_start_iter = int(normal_start_iter), int(dist_start_iter)
         if self.normal_loss or self.dist_loss:
-            if packed or sparse_grad or gaussian_shard or sharded_optimizer or world_size != 1:
-                raise NotImplementedError(
-                    "normal_loss / dist_loss: the one-GPU dense 2DGS trainer only (not packed, "
-                    "Gaussian-sharded, sharded-optimizer or multi-rank trainers)")
+            _refuse("normal_loss / dist_loss", asked)
             if model != "2dgs":
                 raise ValueError("normal_loss / dist_loss are 2DGS terms: model='2dgs'")
         self.model = model
@@ -408,7 +487,6 @@ class Trainer:
             self._app_embed_m = torch.zeros(n_img, _app.EMBED_DIM, device=device)
             self._app_embed_v = torch.zeros(n_img, _app.EMBED_DIM, device=device)
             self._app_grads = torch.zeros(_app.HEAD_NUMEL + _app.EMBED_DIM, device=device)
-            self._app_index = torch.arange(n_img, dtype=torch.int64, device=device)
             self._app_ws = None
             self.app_step_count = 0
             self.app_lr = float(app_opt_lr) * math.sqrt(world_size)
@@ -512,9 +590,8 @@ class Trainer:
             self.bil_lr = 2e-3 * math.sqrt(BS)
             self.bil_opt = FusedAdam([self.bil_grids], [self.bil_lr], betas=(0.9, 0.999),
                                      eps=1e-15)
-            self._bil_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
         self.pose_lr = float(pose_opt_lr) * math.sqrt(BS)
-        if self.pose_opt or self.pose_noise > 0.0:
+        if self.pose_active:
             assert self.geom_in_proj, "pose_opt: the geometry Adam in the projection backward"
             n_img = len(viewmats)
             # utils.py CameraOptModule: embeds.weight [n, 9], zero_init; its
@@ -531,15 +608,16 @@ class Trainer:
                 self.pose_noise_table = (torch.randn(n_img, 9, generator=gp)
                                          * self.pose_noise).to(device)
             self._pose_vm = torch.empty(1, 4, 4, device=device)  # the step's view matrix
-            self._pose_index = torch.arange(n_img, dtype=torch.int64, device=device)
             self._pose_ws = None
         if self.depth_loss:
             # the images' points as CSR tables on the device, built once; the
-            # step names its image by a device index (the captured step: the
-            # camera index of its input block)
+            # step names its image by a device index
             from .depth_loss import DepthPoints
             self.depth_table = DepthPoints(depth_points, device)
-            self._depth_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
+        # an eager step names its image by a one-element view of this table (the
+        # captured step: by the camera index of its input block)
+        self._cam_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
+        self.side_opts = self._side_optimizers()
         self.viewmats = viewmats.to(device)
         self.Ks = Ks.to(device)
         if targets is None:
@@ -585,15 +663,14 @@ class Trainer:
             groups = [[names.index(k) for k in ("means", "scales", "quats", "opacities")],
                       [names.index(k) for k in ("sh0", "shN")]]
             return ShardedAdam(params, self.lrs, groups=groups,
-                               group_pgs=[None, getattr(self, "_sh_pg", None)],
-                               emulate_world=getattr(self, "dp_emulate_world", None),
-                               **self.adam_kw)
+                               group_pgs=[None, self._sh_pg],
+                               emulate_world=self.dp_emulate_world, **self.adam_kw)
         groups = [{"params": [p], "lr": lr, "name": k}
                   for (k, p), lr in zip(self.params.items(), self.lrs)]
-        if getattr(self, "visible_adam", False):
+        if self.visible_adam:
             from ._wrapper_aux import SelectiveAdam
             return SelectiveAdam(groups, **self.adam_kw)
-        if getattr(self, "sparse_grad", False):
+        if self.sparse_grad:
             return torch.optim.SparseAdam(groups, **self.adam_kw)
         if self.fused:  # HIP loss + one-launch Adam (csrc/ssim.hip, csrc/adam.hip)
             return FusedAdam(params, self.lrs, **self.adam_kw)
@@ -625,12 +702,12 @@ class Trainer:
         parameter (gathered over the ranks for the sharded optimizer); with
         the bilateral grid, "bil_grids" holds the grid optimizer's."""
         out = self._gaussian_moments()
-        if getattr(self, "bilateral_grid", False):
+        if self.bilateral_grid:
             out["bil_grids"] = [self.bil_opt.exp_avg[0], self.bil_opt.exp_avg_sq[0]]
-        if getattr(self, "pose_opt", False):
+        if self.pose_opt:
             self.sync()
             out["pose_embeds"] = [self._pose_m, self._pose_v]
-        if getattr(self, "app_opt", False):
+        if self.app_opt:
             self.sync()
             out["app_embeds"] = [self._app_embed_m, self._app_embed_v]
             out["app_head"] = [self._app_head_m, self._app_head_v]  # flat, W1 b1 W2 b2 W3 b3
@@ -671,23 +748,64 @@ class Trainer:
             self._app_ws, self._app_ws_n = app_workspace(n, 1, self.device), n
         return self._app_ws
 
-    def _app_step(self, cam_index, hyper=None, skip=None):
+    def _app_launch(self, s: StepInputs, hyper):
         """After the backward: the ordered sum of the colour backward's partial
         sums and the module's two Adam optimizers in place (head: lr; the
         embedding table: 10 x lr with app_opt_reg as weight decay, dense)."""
         from .appearance import app_reduce_adam
+        if hyper is None:
+            self.app_step_count += 1
         app_reduce_adam(self._app_ws, self.params["means"].shape[0], 1, self._app_grads,
                         self.app_head, self._app_head_m, self._app_head_v, self.app_lr,
                         self.app_step_count, embeds=self.app_embeds,
-                        embed_ids=cam_index, embed_exp_avg=self._app_embed_m,
+                        embed_ids=s.cam, embed_exp_avg=self._app_embed_m,
                         embed_exp_avg_sq=self._app_embed_v,
-                        embed_weight_decay=self.app_opt_reg, hyper=hyper, skip=skip)
+                        embed_weight_decay=self.app_opt_reg, hyper=hyper, skip=s.void)
+
+    def _app_factors(self, it: int):
+        """torch's Adam for the head (lr) and the embedding table (10 x lr)."""
+        from .appearance import BETAS, EMBED_LR_MULT
+        (sh, ib), (se, _) = adam_factors([self.app_lr, self.app_lr * EMBED_LR_MULT], BETAS,
+                                         self.app_step_count + 1)
+        return sh, ib, se, 0.0
+
+    # ----------------------------------------------------- side optimizers
+    def _side_optimizers(self):
+        """The Adam launches after the Gaussians', in launch order: the
+        bilateral grids', the pose table's, the appearance module's."""
+        out = []
+        if self.bilateral_grid:
+            out.append(SideOptimizer("bil", (self.bil_opt, "step_count"), self._bil_factors,
+                                     self._bil_launch))
+        if self.pose_opt:
+            out.append(SideOptimizer("pose", (self, "pose_step_count"), self._pose_factors,
+                                     self._pose_launch, self._pose_workspace))
+        if self.app_opt:
+            out.append(SideOptimizer("app", (self, "app_step_count"), self._app_factors,
+                                     self._app_launch, self._app_workspace))
+        return out
+
+    def _bil_factors(self, it: int):
+        """The grids' Adam: its own betas, the chained schedule's lr."""
+        from .bilagrid import bilagrid_lr
+        bo = self.bil_opt
+        bo.lrs[0] = bilagrid_lr(it, self.max_steps, self.bil_lr)
+        return adam_factors(bo.lrs, bo.betas, bo.step_count + 1)[0]
+
+    def _bil_launch(self, s: StepInputs, hyper):
+        """simple_trainer.py:300-318: the grids' Adam, densely over all images."""
+        if hyper is None:
+            self._bil_factors(s.it)  # (sets this step's learning rate)
+            self.bil_opt.step()
+        else:
+            self.bil_opt.step(hyper=hyper, void=s.void)
+        self.bil_opt.zero_grad()
 
     # ----------------------------------------------------------- pose_opt
     @property
     def pose_active(self) -> bool:
         """The step renders through pose.pose_apply (pose_opt or pose_noise)."""
-        return getattr(self, "pose_opt", False) or getattr(self, "pose_noise", 0.0) > 0.0
+        return self.pose_opt or self.pose_noise > 0.0
 
     def pose_lr_at(self, it: int) -> float:
         """The pose optimizer's learning rate at step `it`: pose_opt_lr sqrt(BS),
@@ -721,8 +839,28 @@ class Trainer:
             return vms[ids].clone()
         out = torch.empty(len(ids), 4, 4, device=vms.device)
         for k, ci in enumerate(ids):
-            self._pose_viewmat(vms[ci:ci + 1], self._pose_index[ci:ci + 1], out=out[k:k + 1])
+            self._pose_viewmat(vms[ci:ci + 1], self._cam_index[ci:ci + 1], out=out[k:k + 1])
         return out
+
+    def _pose_factors(self, it: int):
+        from .pose import BETAS
+        return adam_factors([self.pose_lr_at(it)], BETAS, self.pose_step_count + 1)[0]
+
+    def _pose_launch(self, s: StepInputs, hyper):
+        """Launch (c): the pose gradient from the projection backward's partials
+        and the pose Adam over the whole table."""
+        from .pose import pose_bwd_adam
+        if not self.geom_applied:
+            raise RuntimeError("pose_opt: the projection backward did not run the geometry "
+                               "Adam, so it formed no pose gradient (a loss term outside the "
+                               "render reached the geometry parameters?)")
+        lr, step = 0.0, 1  # unused with the device factors
+        if hyper is None:
+            self.pose_step_count += 1
+            lr, step = self.pose_lr_at(s.it), self.pose_step_count
+        pose_bwd_adam(self._pose_ws, self.params["means"].shape[0], _wrapper._f32c(s.viewmats),
+                      s.cam, self.pose_embeds, self._pose_m, self._pose_v, lr, self.pose_opt_reg,
+                      step, noise=self.pose_noise_table, hyper=hyper, skip=s.void)
 
     def _gaussian_moments(self):
         names = list(self.params)
@@ -744,7 +882,7 @@ class Trainer:
     def _load_moments(self, moments):
         params = list(self.params.values())
         names = list(self.params)
-        if "bil_grids" in moments and getattr(self, "bilateral_grid", False):
+        if "bil_grids" in moments and self.bilateral_grid:
             self.bil_opt.params = [self.bil_grids]
             self.bil_opt.exp_avg = [moments["bil_grids"][0]]
             self.bil_opt.exp_avg_sq = [moments["bil_grids"][1]]
@@ -773,7 +911,7 @@ class Trainer:
         """Order the current stream after any optimizer communication still in
         flight (the sharded optimizer's deferred all-gathers): call before
         reading the parameters outside the training step (checkpoint, eval)."""
-        if getattr(self, "_graph", None) is not None:
+        if self._graph is not None:
             self._graph.sync()
             if self._graph.failed is not None:  # a recovery's re-capture failed
                 self.graph_fallback = self._graph.failed
@@ -785,7 +923,7 @@ class Trainer:
         """Stop replaying: settle the captured step's replays, destroy its
         graph (before destroy_process_group, see GraphStep.release) and issue
         later steps eagerly."""
-        if getattr(self, "_graph", None) is not None:
+        if self._graph is not None:
             self._graph.release()
             self._graph = None
 
@@ -821,10 +959,8 @@ class Trainer:
     def geometry_terms_at(self, it: int):
         """(normal_lambda, dist_lambda) of step `it`, 0.0 for a term that is
         off or not yet started (simple_trainer_2dgs.py:612,627: step > start)."""
-        nl = self.normal_lambda if (getattr(self, "normal_loss", False)
-                                    and it > self.normal_start_iter) else 0.0
-        dl = self.dist_lambda if (getattr(self, "dist_loss", False)
-                                  and it > self.dist_start_iter) else 0.0
+        nl = self.normal_lambda if self.normal_loss and it > self.normal_start_iter else 0.0
+        dl = self.dist_lambda if self.dist_loss and it > self.dist_start_iter else 0.0
         return nl, dl
 
     def camtoworld(self, ci: int) -> torch.Tensor:
@@ -846,82 +982,90 @@ class Trainer:
                                   meta["camtoworlds"], Ks, distort if dl else None,
                                   normal_lambda=nl, dist_lambda=dl, _depth_image=True)
 
-    def render(self, ci: int, sh_degree: Optional[int] = None,
+    def render(self, ci: Optional[int], sh_degree: Optional[int] = None,
                fusion: Optional[_wrapper.StepFusion] = None, world_ci=None, geometry=None,
-               viewmats=None, app_index=None):
+               viewmats=None, Ks=None, camtoworlds=None, cam_index=None, fetch=None,
+               isect=None):
         """Render camera `ci`; `fusion` (a training step's StepFusion) goes to
         the nodes whose backward hands their gradients to the optimizer.
         `geometry` (2DGS): the step's (normal_lambda, dist_lambda); with one
         non-zero the normal and distortion images are rendered too
         (meta["_geometry"], geometry_loss).
-        `viewmats` (3DGS, one rank): a [1,4,4] view matrix instead of camera
-        `ci`'s own (a pose_opt step's adjusted one).
-        `app_index` (app_opt): the device index [1] of the image whose
-        embedding row colours the render; None: the zero embedding.
         Gaussian-sharded: a collective -- every rank renders its own camera
-        with all ranks' Gaussians (`world_ci`: see world_cameras)."""
+        with all ranks' Gaussians (`world_ci`: see world_cameras).
+        A training step (StepInputs) also gives
+        `viewmats` / `Ks`: [W,4,4] / [W,3,3] instead of camera `ci`'s own: W =
+        1, or the Gaussian-sharded world's cameras in rank order;
+        `camtoworlds` (2DGS): the camera's inverse view matrix [1,4,4];
+        `cam_index`: the device index [1] of the step's image -- its pose rows
+        adjust the camera (pose_opt / pose_noise) and its embedding row colours
+        the render (app_opt); None: the camera as given, the zero embedding;
+        `fetch`: strategy.activate's (the captured step's input block);
+        `isect`: the sync-free intersection's rasterization keywords."""
         p = self.params
         deg = self.sh_degree if sh_degree is None else sh_degree
+        isect = isect or {}
         hook = None
-        if self.sharded:
+        if self.sharded and not self.opt.capturing:
             # the previous step's all-gathers: geometry before the projection,
-            # the SH rows only before the colours (evaluated after isect)
+            # the SH rows only before the colours (evaluated after isect); a
+            # captured step leaves none in flight (ShardedAdam.capturing)
             names = list(self.params)
             self.opt.wait([names.index(k) for k in ("means", "scales", "quats", "opacities")])
             sh_idx = [names.index(k) for k in ("sh0", "shN")]
             hook = lambda: self.opt.wait(sh_idx)  # noqa: E731
-        if self.fused and not getattr(self, "sparse_grad", False):
+        if self.fused and not self.sparse_grad:
             # one HIP launch each way for both activations (sparse_grad: torch's,
             # whose backward takes the projection's COO gradients)
-            scales, opac = activate(p["scales"], p["opacities"], fusion)
+            scales, opac = activate(p["scales"], p["opacities"], fusion, fetch=fetch)
         else:
             scales, opac = torch.exp(p["scales"]), torch.sigmoid(p["opacities"])
+        if viewmats is None:
+            vms, K = self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1]
+        else:  # this rank's camera of the step's
+            r = self.rank if self.gshard else 0
+            vms, K = viewmats[r:r + 1], Ks[r:r + 1]
+        if cam_index is not None and self.pose_active:  # launch (a): the step's view matrix
+            vms = self._pose_viewmat(_wrapper._f32c(vms), cam_index)
         absgrad = getattr(self.strategy, "absgrad", False)
         if self.model == "2dgs":
             if hook is not None:
                 hook()
-            if geometry is not None and any(geometry):
-                rc, ra, rn, _, rd, _, meta = rasterization_2dgs(
-                    p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]),
-                    self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1], self.width, self.height,
-                    sh_degree=deg, packed=False, near_plane=0.01, far_plane=1e10,
-                    render_mode="RGB+D", absgrad=absgrad, distloss=bool(geometry[1]),
-                    _fusion=fusion, _camtoworlds=self.camtoworld(ci), _geometry=True)
-                meta["_rgbd"] = rc
-                meta["_geometry"] = (rn, ra, rd)
-                return rc[..., :3], ra, meta
-            rc, ra, _, _, _, _, meta = rasterization_2dgs(
-                p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]),
-                self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1], self.width, self.height,
-                sh_degree=deg, packed=False, near_plane=0.01, far_plane=1e10,
-                render_mode="RGB+D", absgrad=absgrad, _fusion=fusion, _colors_only=True)
+            geo = geometry is not None and any(geometry)
+            if geo:
+                kw = dict(_geometry=True, distloss=bool(geometry[1]),
+                          _camtoworlds=self.camtoworld(ci) if camtoworlds is None else camtoworlds)
+            else:
+                kw = dict(_colors_only=True)
+            rc, ra, rn, _, rd, _, meta = rasterization_2dgs(
+                p["means"], p["quats"], scales, opac, (p["sh0"], p["shN"]), vms, K, self.width,
+                self.height, sh_degree=deg, packed=False, near_plane=0.01, far_plane=1e10,
+                render_mode="RGB+D", absgrad=absgrad, _fusion=fusion, **kw, **isect)
             meta["_rgbd"] = rc  # the loss reads its colour channels in place
+            if geo:
+                meta["_geometry"] = (rn, ra, rd)
             return rc[..., :3], ra, meta
         dkw = {}
-        if getattr(self, "gshard", False):
-            dkw = dict(distributed=True, _world_cameras=self.world_cameras(ci, world_ci),
-                       _world_counts=self._n_world)
-        depth = getattr(self, "depth_loss", False)
-        vms = self.viewmats[ci:ci + 1] if viewmats is None else viewmats
-        if getattr(self, "app_opt", False):
+        if self.gshard:
+            dkw = dict(distributed=True, _world_counts=self._n_world,
+                       _world_cameras=(self.world_cameras(ci, world_ci) if viewmats is None
+                                       else (viewmats, Ks)))
+        if self.app_opt:
             # the colours of the appearance MLP at `deg`, rendered as plain
             # colours (sh_degree None), evaluated after the projection
             coeffs, deg_r = p["colors"], None
-            dkw["_app"] = self._app_colors(vms, deg, app_index, fusion)
+            dkw["_app"] = self._app_colors(vms, deg, cam_index, fusion)
         else:
             coeffs, deg_r = ((p["sh0"], p["shN"]) if self.fused
                              else torch.cat([p["sh0"], p["shN"]], 1)), deg
-        with _wrapper.fwd_split(getattr(self, "split_div", None),
-                                getattr(self, "split_threshold", None)):
+        with _wrapper.fwd_split(self.split_div, self.split_threshold):
             rc, ra, meta = rasterization(
-                p["means"], p["quats"], scales, opac, coeffs, vms,
-                self.Ks[ci:ci + 1], self.width, self.height,
-                sh_degree=deg_r, packed=getattr(self, "packed", False), near_plane=0.01,
-                far_plane=1e10, radius_clip=0.0, rasterize_mode=self.rasterize_mode,
-                absgrad=absgrad, render_mode="RGB+D" if depth else "RGB",
-                sparse_grad=getattr(self, "sparse_grad", False), _colors_ready=hook,
-                _fusion=fusion, **dkw)
-        if depth:  # the losses read the RGB+D render in place (depth_losses)
+                p["means"], p["quats"], scales, opac, coeffs, vms, K, self.width, self.height,
+                sh_degree=deg_r, packed=self.packed, near_plane=0.01, far_plane=1e10,
+                radius_clip=0.0, rasterize_mode=self.rasterize_mode, absgrad=absgrad,
+                render_mode="RGB+D" if self.depth_loss else "RGB", sparse_grad=self.sparse_grad,
+                _colors_ready=hook, _fusion=fusion, **dkw, **isect)
+        if self.depth_loss:  # the losses read the RGB+D render in place (depth_losses)
             meta["_rgbd"] = rc
             return rc[..., :3], ra, meta
         return rc, ra, meta
@@ -934,7 +1078,7 @@ class Trainer:
         the grid is applied to the colour channels alone."""
         from . import depth_loss as _dl
         weight = self.depth_lambda * self.scene_scale
-        if getattr(self, "bilateral_grid", False):
+        if self.bilateral_grid:
             from .bilagrid import _slice_tv
             colors, tv = _slice_tv(self.bil_grids, _dl.colour_channels(rgbd), cam_index,
                                    self.BIL_TV_WEIGHT)
@@ -976,7 +1120,7 @@ class Trainer:
         if self.world_size == 1 and not os.environ.get("GSPLAT_HIP_FWD_SPLIT_DIV"):
             self.split_div = 1100 if self.term_ratio > 0.75 else 550
         n = int(meta["isect_counts"][0]) if "isect_counts" in meta else meta["flatten_ids"].numel()
-        with _wrapper.fwd_split(getattr(self, "split_div", None)):
+        with _wrapper.fwd_split(self.split_div):
             thr = _wrapper.fwd_split_threshold(n)
         self.max_tile_first = _wrapper.max_tile_isects(meta)
         self.split_launch = 1 if 0 <= thr < self.max_tile_first else 0
@@ -985,9 +1129,9 @@ class Trainer:
         del colors, meta
 
     def step(self, it: int):
-        if not getattr(self, "_split_tuned", False):
+        if not self._split_tuned:
             self._tune_split(it)
-        if getattr(self, "_graph", None) is not None:
+        if self._graph is not None:
             from .graph_step import GraphCaptureError
             try:
                 loss = self._graph.step(it)
@@ -1015,71 +1159,113 @@ class Trainer:
     def _eager_step(self, it: int):
         """Training step `it` issued from the host (no refine / reset: post_step)."""
         ci = self.camera_index(it)
-        self._sh_ready = 0
         if self.max_steps:  # means ExponentialLR: this step's lr, before the
             # backward that may run the geometry update (geom_in_proj)
             self._set_means_lr(self.lrs[0] * (0.01 ** (1.0 / self.max_steps)) ** it)
-        fusion = self._make_fusion()
-        terms = self.geometry_terms_at(it)
-        pose_vm = None
-        if self.pose_active:  # launch (a): this step's view matrix
-            pose_vm = self._pose_viewmat(_wrapper._f32c(self.viewmats[ci:ci + 1]),
-                                         self._pose_index[ci:ci + 1])
-        app = getattr(self, "app_opt", False)
-        colors, alphas, meta = self.render(ci, self.sh_degree_at(it), fusion, geometry=terms,
-                                           viewmats=pose_vm,
-                                           app_index=self._app_index[ci:ci + 1] if app else None)
+        vms, Ks = self.world_cameras(ci) if self.gshard else \
+            (self.viewmats[ci:ci + 1], self.Ks[ci:ci + 1])
+        loss, meta = self._run_step(StepInputs(
+            deg=self.sh_degree_at(it), terms=self.geometry_terms_at(it),
+            stats=self.strategy is None or (not self.mcmc
+                                            and it < self.strategy.refine_stop_iter),
+            viewmats=vms, Ks=Ks, cam=self._cam_index[ci:ci + 1], targets=self.targets[ci:ci + 1],
+            c2w=self.camtoworld(ci) if self.model == "2dgs" else None, it=it))
+        self.last_meta = meta
+        return loss
+
+    def _layout(self):
+        """(groups of the Gaussians' Adam launches in launch order, offset of
+        the SH-Adam factors): a captured step's device-side factors
+        (StepInputs.hyper) are laid out in that order."""
+        if self.sharded:
+            idx = [i for sel in self.opt.launch_plan() for i in sel]
+            return idx, 2 * len(idx)
+        names = list(self.params)
+        sh = {names.index(k) for k in ("sh0", "shN") if k in names}
+        idx = [i for i in range(len(names)) if not (self.sh_adam_in_bwd and i in sh)]
+        return idx, 2 * len(idx)
+
+    def _run_step(self, s: StepInputs):
+        """Issue one whole training step -- the only place that does: the
+        fusion, activations, pose adjustment and render; the bilateral grid's
+        slice or the depth losses, the photometric loss, the geometry terms, tv
+        and the regularisers; the backward with the constant seed, the strategy
+        statistics, the Gaussians' Adam and the side optimizers'.  Trainer.
+        _eager_step and GraphStep._body are its callers; they differ in where
+        the inputs `s` live.  Returns (loss, the render's meta)."""
+        self._sh_ready = 0  # the sharded optimizer's SH reduce-scatter hook
+        fusion = self._make_fusion(s)
+        # (the activations first -- a captured step's fetch its input block --
+        # then the pose adjustment: Trainer.render)
+        colors, alphas, meta = self.render(
+            None, s.deg, fusion, geometry=s.terms, viewmats=s.viewmats, Ks=s.Ks,
+            camtoworlds=s.c2w, cam_index=s.cam, fetch=s.fetch, isect=s.isect)
         if self.model == "3dgs":
             # DefaultStrategy.step_pre_backward: the means2d gradient is
-            # captured by a hook (retain_grad would clone it into .grad)
-            meta["means2d"].register_hook(lambda g: meta.__setitem__("means2d_grad", g))
-        gt = self.targets[ci:ci + 1]
+            # captured by a hook (retain_grad would clone it into .grad), into a
+            # box of its own (a hook holding `meta` would tie the render's
+            # tensors and their autograd graph into a reference cycle).  2DGS:
+            # the densification input is a leaf, its .grad read after the
+            # backward (a hook keeping a reference would make AccumulateGrad
+            # clone the gradient -- a memcpy node in a captured step)
+            box = {}
+            meta["means2d"].register_hook(lambda g: box.__setitem__("means2d_grad", g))
         tv = None
-        depth = getattr(self, "depth_loss", False)
-        if getattr(self, "bilateral_grid", False):
+        if self.bilateral_grid and not self.depth_loss:
             # simple_trainer.py:620-630, 663-665: the camera's grid applied to
             # the render, 10 x the grids' total variation added to the loss
-            from .bilagrid import _slice_tv, bilagrid_lr
-            self.bil_opt.lrs[0] = bilagrid_lr(it, self.max_steps, self.bil_lr)
-            if not depth:
-                colors, tv = _slice_tv(self.bil_grids, colors, self._bil_index[ci:ci + 1],
-                                       self.BIL_TV_WEIGHT)
-        if depth:  # simple_trainer.py:647-665: the photometric loss and the depth term
-            photo, term, tv = self.depth_losses(meta["_rgbd"], alphas, gt,
-                                                self._depth_index[ci:ci + 1])
+            from .bilagrid import _slice_tv
+            colors, tv = _slice_tv(self.bil_grids, colors, s.cam, self.BIL_TV_WEIGHT)
+        vote = None
+        if s.vote:  # the ranks' overflow flags, agreed beside the loss kernels
+            import torch.distributed as dist
+            from . import distributed as gdist
+            vote = dist.all_reduce(s.void, op=dist.ReduceOp.MAX, async_op=True,
+                                   group=gdist.current_capture_group())
+        if self.depth_loss:  # simple_trainer.py:647-665: the photometric loss and the depth term
+            photo, term, tv = self.depth_losses(meta["_rgbd"], alphas, s.targets, s.cam,
+                                                gt_index=s.gt_index)
             loss = photo + term
-        elif self.fused and "_rgbd" in meta:  # 2DGS: the RGB+D render in place
-            loss = l1_ssim_loss(meta["_rgbd"], gt, self.ssim_lambda, _channels=3)
-        elif self.fused:
-            loss = l1_ssim_loss(colors, gt, self.ssim_lambda)
+        elif self.fused:  # (2DGS: the RGB+D render's colour channels in place)
+            two = self.model == "2dgs"
+            loss = l1_ssim_loss(meta["_rgbd"] if two else colors, s.targets, self.ssim_lambda,
+                                gt_index=s.gt_index, _out_ring=s.loss_ring,
+                                _channels=3 if two else None)
         else:
-            l1 = F.l1_loss(colors, gt)
-            ssim_loss = 1.0 - ssim(colors.permute(0, 3, 1, 2), gt.permute(0, 3, 1, 2),
+            l1 = F.l1_loss(colors, s.targets)
+            ssim_loss = 1.0 - ssim(colors.permute(0, 3, 1, 2), s.targets.permute(0, 3, 1, 2),
                                    self.window)
             loss = l1 * (1.0 - self.ssim_lambda) + ssim_loss * self.ssim_lambda
-        if any(terms):
-            loss = loss + self.geometry_loss(meta, self.Ks[ci:ci + 1], terms)
+        if any(s.terms):
+            loss = loss + self.geometry_loss(meta, s.Ks, s.terms)
         if tv is not None:
             loss = loss + tv
         loss = self._regularise(loss)
+        if vote is not None:
+            vote.wait()
+            ring, slot = s.isect["_isect_report"]
+            _lib.call("gsplat_hip_status_to_ring", s.void.data_ptr(), ring, slot.data_ptr(),
+                      _wrapper._stream())
         if self.fused and loss.dim() == 0:
-            # a constant 1.0 seed (no fill launch; the fused loss's backward
-            # recognises it and skips its scaling launch)
-            from . import losses as _losses
-            if _losses.ONE_GRAD is None or _losses.ONE_GRAD.device != loss.device:
-                _losses.ONE_GRAD = torch.ones((), device=loss.device)
-            torch.autograd.backward(loss, _losses.ONE_GRAD)
+            torch.autograd.backward(loss, _one_grad(loss.device))
         else:
             loss.backward()
-        if self.world_size > 1 and not self.sharded and not getattr(self, "gshard", False):
+        if self.model == "3dgs":
+            meta.update(box)
+        if self.world_size > 1 and not self.sharded and not self.gshard:
             self.allreduce_grads()
-        if self.strategy is None or (not self.mcmc and it < self.strategy.refine_stop_iter):
-            self.update_state(meta)
+        if s.stats:
+            self.update_state(meta, skip=s.void)
         # whether this step's geometry update ran inside the projection backward
         self.geom_applied = bool(fusion is not None and fusion.geom_adam is not None
                                  and fusion.geom_adam.applied)
-        if self.sharded:
-            self.opt.step(defer_gather=True, xform=self._geom_xform(fusion))
+        xform = self._geom_xform(fusion)
+        hyper = s.hyper
+        if self.sharded:  # reduce-scatter, Adam on this rank's rows, all-gather
+            if hyper is not None:
+                assert not self._sh_skip(fusion)
+                hyper = hyper[:self._layout()[1]]
+            self.opt.step(defer_gather=not s.capturing, xform=xform, hyper=hyper, void=s.void)
         elif self.visible_adam:  # simple_trainer.py:782-797
             if meta.get("gaussian_ids") is not None:  # packed: the Gaussians of the pairs
                 vis = torch.zeros(self.params["opacities"].shape[0], dtype=torch.bool,
@@ -1101,32 +1287,21 @@ class Trainer:
                                                  is_coalesced=meta["n_cameras"] == 1)
             self.opt.step()
         else:
-            self.opt.step(skip=self._sh_skip(fusion), xform=self._geom_xform(fusion))
+            skip = self._sh_skip(fusion)
+            kw = {}
+            if hyper is not None:
+                # the launched groups are the launch plan's tail (the geometry
+                # groups, its head, may have been updated by the projection
+                # backward): their factors start at that offset
+                idx, sh_off = self._layout()
+                launched = tuple(i for i in range(len(self.params)) if i not in skip)
+                assert launched == tuple(idx[len(idx) - len(launched):]), (skip, idx)
+                kw = dict(hyper=hyper[2 * (len(idx) - len(launched)):sh_off], void=s.void)
+            self.opt.step(skip=skip, xform=xform, **kw)
         self.opt.zero_grad(set_to_none=True)
-        if tv is not None:
-            self.bil_opt.step()
-            self.bil_opt.zero_grad()
-        if getattr(self, "pose_opt", False):
-            self._pose_step(it, ci)
-        if app:  # the module's two optimizers, from the colour backward's partial sums
-            self.app_step_count += 1
-            self._app_step(self._app_index[ci:ci + 1])
-        self.last_meta = meta
-        return loss
-
-    def _pose_step(self, it: int, ci: int):
-        """Launch (c) of an eager step: the pose gradient from the projection
-        backward's partials and the pose Adam over the whole table."""
-        from .pose import pose_bwd_adam
-        if not self.geom_applied:
-            raise RuntimeError("pose_opt: the projection backward did not run the geometry "
-                               "Adam, so it formed no pose gradient (a loss term outside the "
-                               "render reached the geometry parameters?)")
-        self.pose_step_count += 1
-        pose_bwd_adam(self._pose_ws, self.params["means"].shape[0],
-                      _wrapper._f32c(self.viewmats[ci:ci + 1]), self._pose_index[ci:ci + 1],
-                      self.pose_embeds, self._pose_m, self._pose_v, self.pose_lr_at(it),
-                      self.pose_opt_reg, self.pose_step_count, noise=self.pose_noise_table)
+        for so in self.side_opts:  # the grids', the pose table's, the appearance module's
+            so.launch(s, s.side_hyper.get(so.name))
+        return loss, meta
 
     def _regularise(self, loss):
         """simple_trainer.py:671-681: the opacity / scale regularisers on the raw
@@ -1139,25 +1314,37 @@ class Trainer:
             loss = loss + self.scale_reg * _mean(torch.abs(torch.exp(p["scales"])))
         return loss
 
-    def _make_fusion(self) -> Optional[_wrapper.StepFusion]:
+    def _make_fusion(self, s: StepInputs) -> Optional[_wrapper.StepFusion]:
         """This step's StepFusion (None when nothing is fused): the SH groups'
-        Adam inside the SH backward (sh_adam_in_bwd) and the geometry groups'
-        gradient transforms inside their Adam (geom_fuse)."""
+        Adam inside the SH backward (sh_adam_in_bwd), the geometry groups'
+        gradient transforms inside their Adam (geom_fuse) or their whole Adam
+        inside the projection backward (geom_in_proj).  With s.hyper the
+        updates read their factors there (Trainer._layout) and the void flag."""
+        fused = isinstance(self.opt, FusedAdam)
+        step = self.opt.step_count + 1 if fused and s.hyper is None else 1  # (unused with s.hyper)
+        names = list(self.params)
+        idx, sh_off = self._layout() if s.hyper is not None else (None, None)
         fa = None
-        if getattr(self, "sh_adam_in_bwd", False) and isinstance(self.opt, FusedAdam):
-            names = list(self.params)
+        if self.sh_adam_in_bwd and fused:
             i0, i1 = names.index("sh0"), names.index("shN")
             o = self.opt
             fa = _wrapper.ShAdamInBackward(
                 self.params["sh0"].data, self.params["shN"].data, o.exp_avg[i0],
                 o.exp_avg_sq[i0], o.exp_avg[i1], o.exp_avg_sq[i1], o.lrs[i0], o.lrs[i1],
-                o.betas, o.eps, o.step_count + 1)
-        geom = getattr(self, "geom_fuse", False) and (isinstance(self.opt, FusedAdam) or
-                                                      self.sharded)
+                o.betas, o.eps, step,
+                hyper=None if s.hyper is None else s.hyper[sh_off:sh_off + 3], skip=s.void)
+        geom = self.geom_fuse and (fused or self.sharded)
         ga = None
-        if getattr(self, "geom_in_proj", False) and isinstance(self.opt, FusedAdam):
-            ga = self.geom_adam_in_backward(self.opt.step_count + 1)
-            if getattr(self, "pose_opt", False):
+        if self.geom_in_proj and fused:
+            hyper = None
+            if s.hyper is not None:
+                # the geometry groups' factors are the first launch groups':
+                # (ss, ib) of means, scales, quats, opacities at [0, 8); the SH
+                # groups follow when their update is not fused into the SH backward
+                assert [names[i] for i in idx][:len(self.GEOM)] == list(self.GEOM), (idx, names)
+                hyper = s.hyper[:2 * len(idx)]
+            ga = self.geom_adam_in_backward(step, hyper=hyper, skip=s.void)
+            if self.pose_opt:
                 ga.pose_ws = self._pose_workspace()
         if fa is None and not geom:
             return None
@@ -1285,7 +1472,7 @@ class Trainer:
     def refine(self, it: int):
         self.sync()
         self.last_meta = None  # its tensors are sized for the old Gaussians
-        if self.world_size > 1 and not getattr(self, "gshard", False):
+        if self.world_size > 1 and not self.gshard:
             # every rank accumulated its own cameras: the batch statistics are
             # the sums (the screen radii: their maximum)
             import torch.distributed as dist
@@ -1309,8 +1496,8 @@ class Trainer:
         if self.radii2d is not None:
             self.radii2d = torch.zeros(n, device=self.device)
         self.refine_log.append((it,) + tuple(counts) + (n,))
-        self._param_gen = getattr(self, "_param_gen", 0) + 1  # a captured step re-captures
-        if getattr(self, "gshard", False) and self.world_size > 1:  # each shard refined alone
+        self._param_gen += 1  # a captured step re-captures
+        if self.gshard and self.world_size > 1:  # each shard refined alone
             from .distributed import all_gather_int32
             self._n_world = all_gather_int32(self.world_size, n, device=self.device)
 
@@ -1357,7 +1544,7 @@ class Trainer:
         dead = torch.sigmoid(params["opacities"].flatten()) <= cfg.min_opacity
         n_reloc = _mcmc.relocate(params, moms, dead, self._binoms, cfg.min_opacity,
                                  generator=self.rng)
-        gshard = getattr(self, "gshard", False) and self.world_size > 1
+        gshard = self.gshard and self.world_size > 1
         cap = -(-cfg.cap_max // self.world_size) if gshard else cfg.cap_max
         n_add = _mcmc.n_to_add(params["means"].shape[0], cap)
         if n_add > 0:
@@ -1372,7 +1559,7 @@ class Trainer:
         self.refine_log.append((it, n_reloc, n_add, n))
         if cfg.verbose:
             print(f"Step {it}: Relocated {n_reloc} GSs. Added {n_add} GSs. Now having {n} GSs.")
-        self._param_gen = getattr(self, "_param_gen", 0) + 1
+        self._param_gen += 1
         if gshard:
             from .distributed import all_gather_int32
             self._n_world = all_gather_int32(self.world_size, n, device=self.device)
@@ -1416,11 +1603,12 @@ class Trainer:
             w.wait()
 
     @torch.no_grad()
-    def update_state(self, meta):
+    def update_state(self, meta, skip=None):
         """DefaultStrategy._update_state for packed=False without the host
         sync of torch.where (default.py:213-262): same sums, masked; the
         screen-radius maximum of state["radii"] while refine_scale2d_stop_iter
-        > 0 (default.py:255-262)."""
+        > 0 (default.py:255-262).  `skip` (the fused dense path, a captured
+        step): the device flag of a void step, which leaves the statistics."""
         if self.strategy is not None:
             key = self.strategy.key_for_gradient
         else:
@@ -1453,7 +1641,7 @@ class Trainer:
             return
         if self.fused:
             update_state_(self.grad2d, self.count, g, meta["radii"], meta["width"],
-                          meta["height"], meta["n_cameras"])
+                          meta["height"], meta["n_cameras"], skip=skip)
             return
         sx = meta["width"] / 2.0 * meta["n_cameras"]
         sy = meta["height"] / 2.0 * meta["n_cameras"]
