@@ -1031,7 +1031,14 @@ __attribute__((amdgpu_waves_per_eu(BwdOcc<PX>::W))) bwd2_kernel(Args a) {
           // this pair misses the wave's q-th 16x4 strip entirely (small
           // Gaussians touch one strip of the band): nothing to add, T unchanged
           if (PX > 1 && __ballot(v0[q] | v1[q]) == 0) continue;
-          ex[q] = f2v{__builtin_amdgcn_exp2f(-s2[q].x), __builtin_amdgcn_exp2f(-s2[q].y)};
+          // clamped to [0, 1] (the exponential's output modifier): a valid
+          // record has s2 >= 0, so nothing changes for it; an indefinite
+          // conic's s2 < -128 at another pixel of the strip would give inf
+          // here and 0 * inf = NaN in the opacity gradient below
+          // (fmed3(x, 0, 1) folds into v_exp_f32's clamp bit: in the gfx950 ISA the
+          // backward kernels have the same instruction and VGPR counts as without)
+          ex[q] = f2v{__builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(-s2[q].x), 0.f, 1.f),
+                      __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(-s2[q].y), 0.f, 1.f)};
           ar[q] = f[5] * ex[q];
           const f2v al = f2v{fminf(ar[q].x, kAlphaMax), fminf(ar[q].y, kAlphaMax)};
           const f2v om = 1.f - al;

@@ -597,7 +597,11 @@ def raster_bwd(means2d, conics, colors, opacities, backgrounds, W, H, ts, offset
             dmx = -aD * (a * dx + b * dy)
             dmy = -aD * (b * dx + cc * dy)
         np.add.at(vcol, g, vcol_t)
-        np.add.at(vop, g, (Da * ex).sum(1, dtype=f32))
+        # (a skipped pair has Da == 0, but ex = exp(-sigma) overflows to inf for
+        # sigma < -88 of an indefinite conic: mask it, 0 * inf is NaN)
+        with np.errstate(all="ignore"):
+            vop_t = np.where(dskip, 0, Da * ex).sum(1, dtype=f32)
+        np.add.at(vop, g, vop_t)
         np.add.at(vm, g, np.stack([dmx.sum(1, dtype=f32), dmy.sum(1, dtype=f32)], -1))
         if absgrad:
             np.add.at(vm_abs, g, np.stack([np.abs(dmx).sum(1, dtype=f32),

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from raster_cases import _garden_scene, close_most  # noqa: F401  (imported from here by other tests)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -24,40 +25,6 @@ def close(a, b, rtol, atol, what=""):
     a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=what)
-
-
-def close_most(a, b, rtol, atol, what="", max_frac=1e-4, min_count=2, rows=False,
-               out_bound=None):
-    """allclose up to a handful of threshold flips: a Gaussian whose alpha is
-    within float rounding of 1/255 (or a pixel whose T is within rounding of
-    1e-4) can land on the other side of the cut in two correct fp32
-    implementations (different FMA contraction / exp).  At most
-    max(min_count, max_frac * n) elements -- or, with rows=True, rows of the
-    last axis (all gradient components of one Gaussian) -- may exceed the
-    tolerance, and each of those by at most `out_bound` in absolute value.
-
-    Default bound: a flip adds or drops one Gaussian of alpha ~1/255 at one
-    pixel, which moves that pixel's colour / alpha by <= 1/255 * |c| and every
-    later contribution by a factor (1 - 1/255): <= 2/255 of the largest value,
-    taken as 0.01 * max|b| (+ atol).  Gradient call sites pass their own."""
-    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad_el = ~np.isclose(a, b, rtol=rtol, atol=atol)
-    bad = bad_el
-    if rows and bad.ndim > 1:
-        bad = bad.reshape(-1, bad.shape[-1]).any(-1)
-    allowed = max(min_count, int(max_frac * bad.size))
-    diff = np.abs(a.astype(np.float64) - b)
-    assert bad.sum() <= allowed, (
-        f"{what}: {bad.sum()} of {bad.size} {'rows' if rows else 'elements'} outside "
-        f"rtol={rtol} atol={atol} (allowed {allowed}); max abs diff {diff.max()}")
-    if out_bound is None:
-        out_bound = 0.01 * float(np.abs(b).max(initial=0.0)) + atol
-    if bad_el.any():
-        worst = float(diff[bad_el].max())
-        assert worst <= out_bound, (
-            f"{what}: an outlier is off by {worst}, beyond the one-flip bound {out_bound}")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -309,24 +276,6 @@ def test_raster_vs_reference(name):
     if use_bg:
         close(grads[4], g["v_backgrounds"], 5e-3, 5e-3, "v_backgrounds")
     close(m2.absgrad, g["v_means2d_abs"], 5e-3, 5e-3, "absgrad")
-
-
-def _garden_scene(n, C, W, H, seed=0, scale=0.02):
-    """test_garden.npz is not available on the GPU box: a synthetic scene of the
-    same statistics (means in [-2,2]^3 in front of C cameras)."""
-    g = torch.Generator().manual_seed(seed)
-    means = (torch.rand(n, 3, generator=g) * 4 - 2)
-    quats = torch.nn.functional.normalize(torch.randn(n, 4, generator=g), dim=-1)
-    scales = torch.rand(n, 3, generator=g) * scale
-    opac = torch.rand(n, generator=g)
-    vm = torch.eye(4)[None].repeat(C, 1, 1)
-    for c in range(C):
-        a = 0.4 * c
-        vm[c, :3, :3] = torch.tensor([[math.cos(a), 0, math.sin(a)], [0, 1, 0],
-                                      [-math.sin(a), 0, math.cos(a)]])
-        vm[c, 2, 3] = 5.0
-    K = torch.tensor([[0.9 * W, 0, W / 2], [0, 0.9 * W, H / 2], [0, 0, 1]])[None].repeat(C, 1, 1)
-    return means, quats, scales, opac, vm, K
 
 
 @pytest.mark.parametrize("D,tile", [(3, 16), (4, 16), (16, 16), (32, 8), (5, 16)])
