@@ -93,7 +93,9 @@ hist_kernel(const uint32_t *__restrict__ keys, int64_t n, const int64_t *__restr
 
 // Exclusive scan of row d (nt entries) in place; the row sum -> totals[d].
 // Device count: only the tiles holding items (tile = tile_items items).
-__global__ void __launch_bounds__(NT)
+// (static: the one kernel here that is no template, and more than one source
+// file includes this header)
+static __global__ void __launch_bounds__(NT)
 scan_kernel(uint32_t *__restrict__ hist, int64_t nt, uint32_t *__restrict__ totals,
             const int64_t *__restrict__ n_dev, int64_t n, int64_t tile_items) {
   __shared__ uint32_t wsum[NT / 64];

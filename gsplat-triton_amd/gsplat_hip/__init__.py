@@ -23,6 +23,7 @@ from ._wrapper_indices import (
 )
 from .appearance import appearance_colors
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
+from .compression import PngCompression
 from .depth_loss import sparse_depth_loss
 from .losses import geometry_loss_2dgs
 from .pose import pose_adjust
@@ -47,6 +48,7 @@ __all__ = [
     "bilagrid_lr",
     "pose_adjust",
     "appearance_colors",
+    "PngCompression",
     "quat_scale_to_covar_preci",
     "compute_relocation",
     "adam",

@@ -198,6 +198,9 @@ _SIGS = {
                                          _p, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_app_reduce_adam": (_i32, [_i32, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _i32, _p,
                                           _p, _f, _f, _f, _f, _f, _f, _i32, _p, _p, _p]),
+    "gsplat_hip_kmeans_l1_assign": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_kmeans_update_workspace_bytes": (_i64, [_i64]),
+    "gsplat_hip_kmeans_update": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_watchdog_arm": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
     "gsplat_hip_watchdog_beat": (_i32, [ctypes.c_char_p]),
     "gsplat_hip_watchdog_set_fallback": (_i32, [_i32, ctypes.c_char_p, _i32]),

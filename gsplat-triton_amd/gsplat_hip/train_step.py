@@ -275,6 +275,7 @@ _REFUSALS = {
     "bilateral_grid": ("the one-GPU dense 3DGS trainer only", ("model='2dgs'",) + _SPARSE + _MANY),
     "normal_loss / dist_loss": ("the one-GPU dense 2DGS trainer only",
                                 ("packed", "sparse_grad") + _MANY),
+    "compression": ("one-GPU trainers only", _MANY),
 }
 
 
@@ -1450,6 +1451,43 @@ class Trainer:
             self.__dict__.pop("_wcam_cache", None)
         return {"psnr": sum(psnrs) / len(psnrs), "ssim": sum(ssims) / len(ssims),
                 "num_images": len(psnrs)}
+
+    @torch.no_grad()
+    def evaluate_compressed(self, compress_dir, cameras=None, viewmats=None, Ks=None,
+                            images=None, compression=None):
+        """simple_trainer.py's run_compression (compression="png"): compress the
+        current parameters into `compress_dir` (compression.PngCompression, or
+        the instance given), decompress them and evaluate what came back --
+        evaluate()'s cameras, render path and metrics (app_opt: the zero
+        embedding), plus `compressed_bytes` (the sum of the file sizes in
+        `compress_dir`) and `num_GS` (the n^2 Gaussians of the grid).  The
+        trainer's parameters, optimizer state and captured step are not
+        touched: the decompressed splats stand in only for these renders."""
+        _refuse("compression", {"gaussian_shard": self.gshard,
+                                "sharded_optimizer": bool(self.sharded),
+                                "world_size": self.world_size != 1},
+                name="evaluate_compressed (compression)")
+        from .compression import PngCompression
+        comp = PngCompression(verbose=False) if compression is None else compression
+        os.makedirs(compress_dir, exist_ok=True)
+        comp.compress(compress_dir, {k: p.data for k, p in self.synced_params().items()})
+        splats = comp.decompress(compress_dir)
+        # the appearance workspace is sized for the Gaussians (a captured step
+        # holds its address): the renders of the n^2 get one of their own
+        keep = {k: self.__dict__[k] for k in ("_app_ws", "_app_ws_n") if k in self.__dict__}
+        saved = self.params
+        try:
+            self.params = {k: splats[k].to(self.device, saved[k].dtype).contiguous()
+                           for k in saved}
+            out = self.evaluate(cameras, viewmats, Ks, images)
+            out["num_GS"] = int(self.params["means"].shape[0])
+        finally:
+            self.params = saved
+            self.__dict__.update(keep)
+        out["compressed_bytes"] = sum(
+            os.path.getsize(os.path.join(compress_dir, f)) for f in os.listdir(compress_dir)
+            if os.path.isfile(os.path.join(compress_dir, f)))
+        return out
 
     # ------------------------------------------------------------ strategy
     def post_step(self, it: int, replayed: bool = False):

@@ -63,7 +63,9 @@ const char *gsplat_hip_last_error(void);
  *     (new entries only, no signature changed): gsplat_hip_depth_loss_fwd /
  *     _bwd / _workspace_bytes (the 3DGS trainer's sparse depth supervision);
  *     gsplat_hip_app_colors_fwd / _bwd, gsplat_hip_app_reduce_adam and
- *     gsplat_hip_app_workspace_bytes (appearance optimisation). */
+ *     gsplat_hip_app_workspace_bytes (appearance optimisation);
+ *     gsplat_hip_kmeans_l1_assign, gsplat_hip_kmeans_update and
+ *     gsplat_hip_kmeans_update_workspace_bytes (splat compression). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1227,6 +1229,37 @@ int gsplat_hip_app_reduce_adam(int C, int64_t N, const void *workspace, float *g
                                float beta1, float beta2, float eps, float embed_lr_mult,
                                float embed_weight_decay, int step, const float *hyper_device,
                                const int32_t *skip_device, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Splat compression (ABI 38, new entries only; gsplat/compression/
+ * png_compression.py _compress_kmeans, csrc/compress.hip): the two passes of a
+ * Lloyd iteration over points x[N,D] and centroids[K,D], 1 <= N < 2^31,
+ * 1 <= K <= 65536 (labels are stored as uint16), 1 <= D <= 72 (shN of degrees
+ * 1-3 is D = 9, 24, 45, read in place as [N, K_sh - 1, 3]); otherwise status 1.
+ * The reference hands the clustering to a library (torchpq KMeans,
+ * distance="manhattan"); this is its iteration as far as that call shows: an
+ * L1 assignment and a mean update.
+ *
+ * _assign: labels[i] = argmin_k sum_d |x[i,d] - centroids[k,d]|, the lowest k
+ *   on a tie; each distance is one fp32 sum over d = 0 .. D-1 in order, so the
+ *   same input gives the same labels in every run.  dist[N] (may be NULL):
+ *   the distance to the chosen centroid.  n_changed (device int32, may be
+ *   NULL): zeroed by a kernel, then the number of i whose label differs from
+ *   the INCOMING labels[i] (so labels is read before it is written; the first
+ *   call wants it initialised, e.g. to -1).  Two launches with n_changed, one
+ *   without.
+ * _update: centroids[k] = the arithmetic mean of the rows x[i] with
+ *   labels[i] == k, in place; a centroid without members keeps its value;
+ *   counts[K] = members.  labels must lie in [0, K).  No float atomics: the
+ *   point ids are sorted by label and each centroid's rows are added in
+ *   ascending i, in double, rounded once: bit-identical between calls.
+ *   workspace = gsplat_hip_kmeans_update_workspace_bytes(N) of uninitialised
+ *   memory, 16-B aligned. */
+int gsplat_hip_kmeans_l1_assign(int64_t N, int K, int D, const float *x, const float *centroids,
+                                int32_t *labels, float *dist, int32_t *n_changed, void *stream);
+int64_t gsplat_hip_kmeans_update_workspace_bytes(int64_t N);
+int gsplat_hip_kmeans_update(int64_t N, int K, int D, const float *x, const int32_t *labels,
+                             float *centroids, int32_t *counts, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
