@@ -14,6 +14,7 @@ from ._wrapper import (
     spherical_harmonics,
 )
 from ._wrapper_aux import SelectiveAdam, adam, compute_relocation, quat_scale_to_covar_preci
+from ._wrapper_covar import proj, world_to_cam
 from ._wrapper_2dgs import fully_fused_projection_2dgs, rasterize_to_pixels_2dgs
 from ._wrapper_indices import (
     accumulate,
@@ -50,6 +51,8 @@ __all__ = [
     "appearance_colors",
     "PngCompression",
     "quat_scale_to_covar_preci",
+    "world_to_cam",
+    "proj",
     "compute_relocation",
     "adam",
     "SelectiveAdam",

@@ -156,6 +156,22 @@ _SIGS = {
     "gsplat_hip_projection_packed_bwd": (_i32, [_i32, _i32, _i64, _p, _p, _p, _p, _p, _i32, _i32,
                                                 _f, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p,
                                                 _p, _p, _p]),
+    "gsplat_hip_projection_covar_fwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _i32, _i32, _f, _f, _f,
+                                               _f, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_projection_covar_bwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _i32, _i32, _f, _p, _p,
+                                               _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_projection_covar_packed_count": (_i32, [_i32, _i32, _p, _p, _p, _p, _i32, _i32,
+                                                        _f, _f, _f, _f, _p, _p, _p]),
+    "gsplat_hip_projection_covar_packed_fwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _i32, _i32, _f,
+                                                      _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                      _p]),
+    "gsplat_hip_projection_covar_packed_bwd": (_i32, [_i32, _i32, _i64, _p, _p, _p, _p, _i32,
+                                                      _i32, _f, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                      _i32, _p, _p, _p, _p]),
+    "gsplat_hip_world_to_cam_fwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_world_to_cam_bwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_proj_fwd": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p]),
+    "gsplat_hip_proj_bwd": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p]),
     "gsplat_hip_rasterize_to_indices_count": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                                      _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p,
                                                      _p, _p, _p]),

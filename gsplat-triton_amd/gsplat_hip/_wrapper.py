@@ -254,9 +254,9 @@ class _FullyFusedProjectionPacked(torch.autograd.Function):
 
 def fully_fused_projection(
     means: Tensor,  # [N, 3]
-    covars: Optional[Tensor],  # must be None (quats/scales path only, as the Triton backend)
-    quats: Optional[Tensor],  # [N, 4]
-    scales: Optional[Tensor],  # [N, 3]
+    covars: Optional[Tensor],  # [N, 6] or None
+    quats: Optional[Tensor],  # [N, 4] or None
+    scales: Optional[Tensor],  # [N, 3] or None
     viewmats: Tensor,  # [C, 4, 4]
     Ks: Tensor,  # [C, 3, 3]
     width: int,
@@ -271,7 +271,13 @@ def fully_fused_projection(
     camera_model: str = "pinhole",
     block_size: int = 256,
 ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
-    """Projects Gaussians to 2D (gsplat/triton_impl/_wrapper.py:429-541).
+    """Projects Gaussians to 2D (gsplat/triton_impl/_wrapper.py:429-541,
+    gsplat/cuda/_wrapper.py:209-345).
+
+    The Gaussians are given either by `quats` and `scales` or by `covars`
+    [N, 6], the flattened upper triangle (xx, xy, xz, yy, yz, zz) of their
+    covariances; with `covars`, `quats` and `scales` are ignored and may be
+    None (csrc/projection_covar.hip).  Both forms cull and write alike.
 
     Returns radii i32[C,N], means2d [C,N,2], depths [C,N], conics [C,N,3],
     compensations [C,N] or None.  Entries with radii == 0 are invalid (written
@@ -279,13 +285,30 @@ def fully_fused_projection(
     returns (camera_ids, gaussian_ids, radii, means2d, depths, conics,
     compensations) over the nnz kept pairs, as the CUDA backend
     (gsplat/cuda/_wrapper.py:998-1190); sparse_grad makes the gradients of
-    means/quats/scales COO tensors."""
+    means/quats/scales (or means/covars) COO tensors.  The gradient of
+    `covars` keeps the reference's convention: diagonal entries as they are,
+    off-diagonal entries v[i][j] + v[j][i].  Only camera_model="pinhole" is
+    implemented; any other raises NotImplementedError."""
     C = viewmats.size(0)
     N = means.size(0)
     assert means.size() == (N, 3), means.size()
     assert viewmats.size() == (C, 4, 4), viewmats.size()
     assert Ks.size() == (C, 3, 3), Ks.size()
-    assert covars is None
+    if camera_model != "pinhole":
+        raise NotImplementedError(f"Unsupported camera model: {camera_model}")
+    if covars is not None:
+        from . import _wrapper_covar as _wc
+        assert covars.size() == (N, 6), covars.size()
+        if sparse_grad:
+            assert packed, "sparse_grad is only supported when packed is True"
+        if packed:
+            return _wc._FullyFusedProjectionCovarPacked.apply(
+                means.contiguous(), covars.contiguous(), viewmats.contiguous(), Ks.contiguous(),
+                width, height, eps2d, near_plane, far_plane, radius_clip, sparse_grad,
+                calc_compensations)
+        return _wc._FullyFusedProjectionCovar.apply(
+            means, covars, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+            radius_clip, calc_compensations)
     assert quats is not None, "covars or quats is required"
     assert scales is not None, "covars or scales is required"
     assert quats.size() == (N, 4), quats.size()

@@ -85,6 +85,12 @@ def rasterization(
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Rasterize N 3D Gaussians to C images (gsplat/rendering.py:44-598).
 
+    `covars` [N, 3, 3]: the Gaussians' covariances; `quats` and `scales` are
+    then ignored and may be None (gsplat/rendering.py:246-254).  The upper
+    triangle goes to the projection from covariances
+    (csrc/projection_covar.hip); everything after it is unchanged.  Not with
+    distributed=True.
+
     Private arguments of the training harness (train_step.Trainer):
     `_colors_ready` (see below) and `_fusion`, a _wrapper.StepFusion handed
     to the fused SH-colour node (optimizer work folded into its backward);
@@ -117,8 +123,12 @@ def rasterization(
         assert scales.shape == (N, 3), scales.shape
     else:
         assert covars.shape == (N, 3, 3), covars.shape
-        raise NotImplementedError("covars input is not supported by this backend "
-                                  "(same as the Triton backend, _wrapper.py:517-523)")
+        if distributed:
+            raise NotImplementedError("covars with distributed=True is not supported: the "
+                                      "Gaussian-sharded render takes quats and scales")
+        quats, scales = None, None  # ignored (gsplat/rendering.py:246-254)
+        tri_indices = ([0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2])
+        covars = covars[..., tri_indices[0], tri_indices[1]]  # [N, 6]
     assert opacities.shape == (N,), opacities.shape
     assert viewmats.shape == (C, 4, 4), viewmats.shape
     assert Ks.shape == (C, 3, 3), Ks.shape
@@ -169,14 +179,14 @@ def rasterization(
     # (StepFusion.geom_adam): one camera, dense, no pose gradient
     geom_adam = (_fusion is not None and _fusion.geom_adam is not None and not packed
                  and not distributed and C == 1 and rasterize_mode == "classic"
-                 and not viewmats.requires_grad)
+                 and not viewmats.requires_grad and covars is None)
     if geom_adam:
         proj = _wrapper._FullyFusedProjection.apply(
             means, None, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
             far_plane, radius_clip, False, camera_model, 256, _fusion)
     else:
         proj = fully_fused_projection(
-            means, None, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, packed=packed,
+            means, covars, quats, scales, viewmats, Ks, width, height, eps2d=eps2d, packed=packed,
             near_plane=near_plane, far_plane=far_plane, radius_clip=radius_clip,
             sparse_grad=sparse_grad, calc_compensations=(rasterize_mode == "antialiased"),
             camera_model=camera_model)

@@ -940,6 +940,82 @@ int gsplat_hip_projection_packed_bwd(int C, int N, int64_t nnz, const float *mea
                                      float *v_viewmats, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Projection of Gaussians given by covariances (csrc/projection_covar.hip;
+ * additive, ABI unchanged).
+ *
+ * The fused pinhole projection of gsplat_hip_projection_fwd / _bwd and its
+ * packed form, reading covars[N,6] (upper triangle xx, xy, xz, yy, yz, zz;
+ * rows 8-B aligned) in place of quats / scales
+ * (gsplat/cuda/csrc/ProjectionEWA3DGSFused.cu:74-98, _wrapper.py:209-345).
+ * Arguments, culling, outputs and the packed three-call protocol (with the
+ * workspace of gsplat_hip_projection_packed_workspace_bytes) are those of the
+ * quats / scales entry points.  The backward writes v_means[N,3] and
+ * v_covars[N,6] -- diagonal entries as they are, off-diagonal entries
+ * v[i][j] + v[j][i] (ProjectionEWA3DGSFused.cu:453-464) -- by stores for
+ * C == 1, else zero fill and atomics; sparse_grad: one row per packed entry;
+ * v_viewmats[C,4,4] or NULL. */
+int gsplat_hip_projection_covar_fwd(int C, int N, const float *means, const float *covars,
+                                    const float *viewmats, const float *Ks, int width, int height,
+                                    float eps2d, float near_plane, float far_plane,
+                                    float radius_clip, int32_t *radii, float *means2d,
+                                    float *depths, float *conics, float *compensations,
+                                    void *stream);
+int gsplat_hip_projection_covar_bwd(int C, int N, const float *means, const float *covars,
+                                    const float *viewmats, const float *Ks, int width, int height,
+                                    float eps2d, const int32_t *radii, const float *conics,
+                                    const float *compensations, const float *v_means2d,
+                                    const float *v_depths, const float *v_conics,
+                                    const float *v_compensations, float *v_means, float *v_covars,
+                                    float *v_viewmats, void *stream);
+int gsplat_hip_projection_covar_packed_count(int C, int N, const float *means,
+                                             const float *covars, const float *viewmats,
+                                             const float *Ks, int width, int height, float eps2d,
+                                             float near_plane, float far_plane, float radius_clip,
+                                             void *workspace, int64_t *nnz_device, void *stream);
+int gsplat_hip_projection_covar_packed_fwd(int C, int N, const float *means, const float *covars,
+                                           const float *viewmats, const float *Ks, int width,
+                                           int height, float eps2d, float near_plane,
+                                           float far_plane, float radius_clip,
+                                           const void *workspace, int64_t *camera_ids,
+                                           int64_t *gaussian_ids, int32_t *radii, float *means2d,
+                                           float *depths, float *conics, float *compensations,
+                                           void *stream);
+int gsplat_hip_projection_covar_packed_bwd(int C, int N, int64_t nnz, const float *means,
+                                           const float *covars, const float *viewmats,
+                                           const float *Ks, int width, int height, float eps2d,
+                                           const int64_t *camera_ids, const int64_t *gaussian_ids,
+                                           const float *conics, const float *compensations,
+                                           const float *v_means2d, const float *v_depths,
+                                           const float *v_conics, const float *v_compensations,
+                                           int sparse_grad, float *v_means, float *v_covars,
+                                           float *v_viewmats, void *stream);
+
+/* The unfused stages (gsplat/cuda/_wrapper.py:19-53,176-206,628-760).
+ * world_to_cam: means[N,3], covars[N,3,3] (any 3x3), viewmats[C,4,4] ->
+ * means_c[C,N,3] = R m + t, covars_c[C,N,3,3] = R S R^T; either output may be
+ * NULL.  Backward: each of v_means[N,3], v_covars[N,3,3], v_viewmats[C,4,4]
+ * may be NULL (not computed), as may either cotangent (zeros).
+ * proj: means[C,N,3], covars[C,N,3,3], Ks[C,3,3] -> means2d[C,N,2] (8-B
+ * aligned), covars2d[C,N,2,2] (16-B aligned); camera_model 0 pinhole (with
+ * the 15 % screen-margin clamp), 1 ortho, 2 fisheye; no culling, no blur.
+ * Backward: v_covars2d is a general 2x2 cotangent; v_means[C,N,3] and
+ * v_covars[C,N,3,3] may each be NULL, as may either cotangent; Ks gets no
+ * gradient. */
+int gsplat_hip_world_to_cam_fwd(int C, int N, const float *means, const float *covars,
+                                const float *viewmats, float *means_c, float *covars_c,
+                                void *stream);
+int gsplat_hip_world_to_cam_bwd(int C, int N, const float *means, const float *covars,
+                                const float *viewmats, const float *v_means_c,
+                                const float *v_covars_c, float *v_means, float *v_covars,
+                                float *v_viewmats, void *stream);
+int gsplat_hip_proj_fwd(int C, int N, int camera_model, const float *means, const float *covars,
+                        const float *Ks, int width, int height, float *means2d, float *covars2d,
+                        void *stream);
+int gsplat_hip_proj_bwd(int C, int N, int camera_model, const float *means, const float *covars,
+                        const float *Ks, int width, int height, const float *v_means2d,
+                        const float *v_covars2d, float *v_means, float *v_covars, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Per-pixel contributor lists (§8 f4).  Replace rasterize_to_indices_3dgs /
  * _2dgs (gsplat/cuda/csrc/RasterizeToIndices3DGS.cu:14-185,
  * RasterizeToIndices2DGS.cu:14-200) and their two-pass host driver
