@@ -29,6 +29,7 @@ from .depth_loss import sparse_depth_loss
 from .losses import geometry_loss_2dgs
 from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
+from .undistort import remap_bilinear, undistort_images
 
 __all__ = [
     "fully_fused_projection",
@@ -60,5 +61,7 @@ __all__ = [
     "rasterize_to_indices_in_range_2dgs",
     "accumulate",
     "accumulate_2dgs",
+    "undistort_images",
+    "remap_bilinear",
 ]
 __version__ = "0.1.0"

@@ -18,6 +18,7 @@ _p = ctypes.c_void_p
 _i32 = ctypes.c_int
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
+_d = ctypes.c_double
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -217,6 +218,9 @@ _SIGS = {
     "gsplat_hip_kmeans_l1_assign": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_kmeans_update_workspace_bytes": (_i64, [_i64]),
     "gsplat_hip_kmeans_update": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_undistort_u8_f32": (_i32, [_i32, _i32, _i32, _p] + [_d] * 12
+                                    + [_i32, _i32, _i32, _i32, _i32, _f, _p, _p]),
+    "gsplat_hip_remap_u8_f32": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _i32, _f, _p, _p]),
     "gsplat_hip_watchdog_arm": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
     "gsplat_hip_watchdog_beat": (_i32, [ctypes.c_char_p]),
     "gsplat_hip_watchdog_set_fallback": (_i32, [_i32, ctypes.c_char_p, _i32]),

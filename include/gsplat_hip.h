@@ -1338,6 +1338,40 @@ int gsplat_hip_kmeans_update(int64_t N, int K, int D, const float *x, const int3
                              float *centroids, int32_t *counts, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Image undistortion (ABI 38, new entries only; csrc/undistort.hip): the
+ * device form of cv2.remap(image, mapx, mapy, INTER_LINEAR) with a constant 0
+ * border and the ROI crop (examples/datasets/colmap.py:258-325, 366-374).
+ * images[B,H,W,3] uint8 -> out[B,h,w,3] float32 (4-B aligned, any offset
+ * otherwise), out = scale * the bilinear blend of the four uint8 neighbours of
+ * the pixel's source coordinate, fp32 weights at the unquantised coordinate
+ * (cv2 quantises them to 1/32 px); a neighbour outside the source, or a
+ * coordinate that is not finite, contributes 0.  The B images share one map.
+ * Each image holds fewer than 2^31 bytes (source) and floats (output);
+ * otherwise status 1.  No atomics: bit-identical between calls.
+ *
+ * _undistort_u8_f32: the source coordinate of output pixel (u, v), that is
+ *   pixel (U, V) = (u + roi_x, v + roi_y) of the undistorted full frame, is
+ *   evaluated in the kernel in float64 and rounded to float32.  With
+ *   x = (U - new_cx) / new_fx, y = (V - new_cy) / new_fy, r2 = x^2 + y^2:
+ *   model 0 (perspective; OpenCV initUndistortRectifyMap, R = I):
+ *     kr = 1 + (k2 r2 + k1) r2;  p1 = k3, p2 = k4 of the argument list
+ *     xd = x kr + 2 p1 x y + p2 (r2 + 2 x^2);  yd = y kr + p1 (r2 + 2 y^2) + 2 p2 x y
+ *     source = (fx xd + cx, fy yd + cy)
+ *   model 1 (fisheye; colmap.py:281-316, where new K = K):
+ *     r = 1 + k1 r2 + k2 r2^2 + k3 r2^3 + k4 r2^4
+ *     source = (fx x r + W / 2, fy y r + H / 2)   (integer halves)
+ * _remap_u8_f32: the source coordinates are read from mapx, mapy [h,w]
+ *   float32 instead. */
+int gsplat_hip_undistort_u8_f32(int B, int H, int W, const uint8_t *images, double fx, double fy,
+                                double cx, double cy, double k1, double k2, double k3, double k4,
+                                double new_fx, double new_fy, double new_cx, double new_cy,
+                                int roi_x, int roi_y, int w, int h, int model, float scale,
+                                float *out, void *stream);
+int gsplat_hip_remap_u8_f32(int B, int H, int W, const uint8_t *images, const float *mapx,
+                            const float *mapy, int w, int h, float scale, float *out,
+                            void *stream);
+
+/* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
  * the process when no progress is reported within a timeout: a collective one
  * rank never joins -- also one replayed inside a HIP graph, which RCCL's own
