@@ -11,33 +11,11 @@
 // caller holds them ([N,3] means, [N,4] quats, [N,3] scales).
 #include "common.h"
 #include "geom_adam.h"
+#include "proj_math.h"
 #include "wave_ops.h"
 #include "../../include/gsplat_hip.h"
 
 namespace gs {
-
-struct Cam {
-  M3 R;
-  float t[3];
-  float fx, fy, cx, cy;
-};
-
-GS_INLINE Cam load_cam(const float *__restrict__ viewmats, const float *__restrict__ Ks, int c) {
-  Cam k;
-  const float *V = viewmats + c * 16;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) k.R.m[i][j] = V[i * 4 + j];
-    k.t[i] = V[i * 4 + 3];
-  }
-  const float *K = Ks + c * 9;
-  k.fx = K[0];
-  k.fy = K[4];
-  k.cx = K[2];
-  k.cy = K[5];
-  return k;
-}
 
 // Covariance in world space: (R S)(R S)^T (quat_scale_to_covar.py:7-64).
 GS_INLINE M3 covar_world(const M3 &Rq, float s0, float s1, float s2) {
@@ -49,39 +27,6 @@ GS_INLINE M3 covar_world(const M3 &Rq, float s0, float s1, float s2) {
     RS.m[i][2] = Rq.m[i][2] * s2;
   }
   return mul(RS, transpose(RS));
-}
-
-struct ProjOut {
-  float mx, my;             // projected mean
-  float cxx, cxy, cyy;      // 2D covariance (before blur)
-  float Jxx, Jxz, Jyy, Jyz; // Jacobian (clamped screen coordinates)
-  bool clamp_x, clamp_y;
-};
-
-// Pinhole projection with the 15% screen-margin clamp (cam_proj.py:5-81).
-GS_INLINE ProjOut persp(float x, float y, float z, const M3 &Cc, const Cam &k, int W, int H) {
-  ProjOut o;
-  float iz = 1.f / z;
-  float marx = 0.15f * (float)W / k.fx;
-  float mary = 0.15f * (float)H / k.fy;
-  float lox = -marx - k.cx / k.fx, hix = marx + ((float)W - k.cx) / k.fx;
-  float loy = -mary - k.cy / k.fy, hiy = mary + ((float)H - k.cy) / k.fy;
-  float sx = x * iz, sy = y * iz;
-  o.clamp_x = (sx < lox) | (sx > hix);
-  o.clamp_y = (sy < loy) | (sy > hiy);
-  sx = fminf(fmaxf(sx, lox), hix);
-  sy = fminf(fmaxf(sy, loy), hiy);
-  o.Jxx = k.fx * iz;
-  o.Jxz = -k.fx * sx * iz;
-  o.Jyy = k.fy * iz;
-  o.Jyz = -k.fy * sy * iz;
-  const float(*c)[3] = Cc.m;
-  o.cxx = o.Jxx * c[0][0] * o.Jxx + 2.f * o.Jxx * c[0][2] * o.Jxz + o.Jxz * c[2][2] * o.Jxz;
-  o.cxy = o.Jxx * (c[0][1] * o.Jyy + c[0][2] * o.Jyz) + o.Jxz * (c[1][2] * o.Jyy + c[2][2] * o.Jyz);
-  o.cyy = o.Jyy * c[1][1] * o.Jyy + 2.f * o.Jyy * c[1][2] * o.Jyz + o.Jyz * c[2][2] * o.Jyz;
-  o.mx = k.fx * x * iz + k.cx;
-  o.my = k.fy * y * iz + k.cy;
-  return o;
 }
 
 struct ProjFwdArgs {
@@ -114,6 +59,7 @@ __global__ void __launch_bounds__(256) projection_fwd_kernel(ProjFwdArgs a) {
   const float m0 = mp[0], m1 = mp[1], m2 = mp[2];
 
   const M3 C3 = covar_world(quat_to_rotmat(q.x, q.y, q.z, q.w), s0, s1, s2);
+  // mirrors world_to_cam_mean (proj_math.h): calling it changed this kernel's code
   float mc[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -125,56 +71,7 @@ __global__ void __launch_bounds__(256) projection_fwd_kernel(ProjFwdArgs a) {
   bool keep = in & (mc[2] > a.near_plane) & (mc[2] < a.far_plane);
 
   ProjOut p = persp(mc[0], mc[1], mc[2], Cc, k, a.W, a.H);
-  // add blur (util_kernels.py:64-94)
-  const float det0 = p.cxx * p.cyy - p.cxy * p.cxy;
-  const float bxx = p.cxx + a.eps2d, byy = p.cyy + a.eps2d;
-  const float det = bxx * byy - p.cxy * p.cxy;
-  keep &= det > 0.f;
-  const float inv_det = 1.f / det;
-  const float b = 0.5f * (bxx + byy);
-  const float v1 = b + sqrtf(fmaxf(0.01f, b * b - det));
-  const float r = ceilf(3.f * sqrtf(v1));
-  keep &= (r > a.radius_clip) & (p.mx + r > 0.f) & (p.mx - r < (float)a.W) &
-          (p.my + r > 0.f) & (p.my - r < (float)a.H);
-
-  if (MODE == 0) {
-    a.radii[idx] = keep ? (int32_t)r : 0;
-    float2 m2d = keep ? make_float2(p.mx, p.my) : make_float2(0.f, 0.f);
-    *reinterpret_cast<float2 *>(a.means2d + 2 * idx) = m2d;
-    float *cn = a.conics + 3 * idx;
-    cn[0] = keep ? inv_det * byy : 0.f;
-    cn[1] = keep ? -inv_det * p.cxy : 0.f;
-    cn[2] = keep ? inv_det * bxx : 0.f;
-    if (a.comps) a.comps[idx] = keep ? sqrtf(fmaxf(det0 / det, 0.f)) : 0.f;
-    return;
-  }
-  // packed: rank of this pair among the block's kept pairs (wave ballots)
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint64_t m = __ballot(keep);
-  if (lane == 0) wave_cnt[wid] = __popcll(m);
-  __syncthreads();
-  const int64_t blk = (int64_t)c * gridDim.x + blockIdx.x;
-  if (MODE == 1) {
-    if (threadIdx.x == 0) a.block_cnt[blk] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    return;
-  }
-  if (!keep) return;
-  int before = 0;
-  for (int w = 0; w < wid; ++w) before += wave_cnt[w];
-  const int64_t o = a.block_off[blk] + before +
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-  a.camera_ids[o] = c;
-  a.gaussian_ids[o] = n;
-  a.radii[o] = (int32_t)r;
-  *reinterpret_cast<float2 *>(a.means2d + 2 * o) = make_float2(p.mx, p.my);
-  a.depths[o] = mc[2];
-  float *cn = a.conics + 3 * o;
-  cn[0] = inv_det * byy;
-  cn[1] = -inv_det * p.cxy;
-  cn[2] = inv_det * bxx;
-  if (a.comps) a.comps[o] = sqrtf(fmaxf(det0 / det, 0.f));
+  ewa_fwd_tail<MODE>(a, c, n, idx, keep, mc[2], p);
 }
 
 // Exclusive scan of the packed per-block counts in place, total -> total[0]
@@ -241,18 +138,14 @@ struct ProjBwdArgs {
 // no longer gsplat_hip_projection_bwd_adam's bit for bit (measured).
 GS_INLINE void pose_partials(const ProjBwdArgs &a, const Cam &k, int W, int H, size_t idx,
                              size_t n, float (&vR)[3][3], float (&vt)[3]) {
-  const float *cn = a.conics + 3 * idx;
-  const float ca = cn[0], cb = cn[1], cc = cn[2];
-  const float *vc = a.v_conics + 3 * idx;
-  const float va = vc[0], vb = 0.5f * vc[1], vcc = vc[2];
-  const float dxx = -(ca * va * ca + cb * vcc * cb + 2.f * cb * vb * ca);
-  const float dxy = -(ca * vb * cc + cb * vb * cb + cb * vcc * cc + ca * va * cb);
-  const float dyy = -(cb * va * cb + cc * vcc * cc + 2.f * cc * vb * cb);
+  const Sym2 d = conic_blur_vjp<false>(a, idx);  // no compensations here
+  const float dxx = d.xx, dxy = d.xy, dyy = d.yy;
   const float4 q = *reinterpret_cast<const float4 *>(a.quats + 4 * n);
   const float *sp = a.scales + 3 * n;
   const float *mp = a.means + 3 * n;
   const float m[3] = {mp[0], mp[1], mp[2]};
   const M3 C3 = covar_world(quat_to_rotmat(q.x, q.y, q.z, q.w), sp[0], sp[1], sp[2]);
+  // mirrors world_to_cam_mean (proj_math.h): calling it changed the pose kernel's code
   float mc[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -260,6 +153,7 @@ GS_INLINE void pose_partials(const ProjBwdArgs &a, const Cam &k, int W, int H, s
   const M3 Cc = mul(mul(k.R, C3), transpose(k.R));
   const ProjOut p = persp(mc[0], mc[1], mc[2], Cc, k, W, H);
   const float iz = 1.f / mc[2];
+  // mirrors persp_vjp<true> (proj_math.h): calling it changed the pose kernel's code
   M3 v3;
   v3.m[0][0] = p.Jxx * dxx * p.Jxx;
   v3.m[1][1] = p.Jyy * dyy * p.Jyy;
@@ -309,6 +203,7 @@ GS_INLINE void pose_partials(const ProjBwdArgs &a, const Cam &k, int W, int H, s
 template <bool FUSE = false, bool POSE = false>
 __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
   const bool packed = a.camera_ids != nullptr;
+  // mirrors decode_pair (proj_math.h): calling it changed this kernel's code
   int c, n;
   size_t idx;
   bool valid;
@@ -359,23 +254,8 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
   float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
 
   if (valid) {
-    // ---- conic inverse VJP (util_kernels.py:27-61); v_conic_xy halved
-    const float *cn = a.conics + 3 * idx;
-    const float ca = cn[0], cb = cn[1], cc = cn[2];
-    const float *vc = a.v_conics + 3 * idx;
-    const float va = vc[0], vb = 0.5f * vc[1], vcc = vc[2];
-    float dxx = -(ca * va * ca + cb * vcc * cb + 2.f * cb * vb * ca);
-    float dxy = -(ca * vb * cc + cb * vb * cb + cb * vcc * cc + ca * va * cb);
-    float dyy = -(cb * va * cb + cc * vcc * cc + 2.f * cc * vb * cb);
-    if (a.comps) {  // blur VJP (util_kernels.py:97-144)
-      const float cp = a.comps[idx], vcp = a.v_comps[idx];
-      const float det_i = ca * cc - cb * cb;
-      const float Da = 0.5f * vcp / (cp + 1e-6f);
-      const float oma = 1.f - cp * cp;
-      dxx += Da * (oma * ca - a.eps2d * det_i);
-      dxy += Da * (oma * cb);
-      dyy += Da * (oma * cc - a.eps2d * det_i);
-    }
+    const Sym2 d = conic_blur_vjp(a, idx);
+    const float dxx = d.xx, dxy = d.xy, dyy = d.yy;
     // ---- recompute the forward intermediates
     const float4 q = *reinterpret_cast<const float4 *>(a.quats + 4 * (size_t)n);
     const float *sp = a.scales + 3 * (size_t)n;
@@ -384,6 +264,7 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
     const float m[3] = {mp[0], mp[1], mp[2]};
     const M3 Rq = quat_to_rotmat(q.x, q.y, q.z, q.w);
     const M3 C3 = covar_world(Rq, s0, s1, s2);
+    // mirrors world_to_cam_mean (proj_math.h): calling it changed this kernel's code
     float mc[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -393,6 +274,7 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
     const float iz = 1.f / mc[2];
 
     // ---- perspective VJP (cam_proj.py:84-242)
+    // mirrors persp_vjp<true> (proj_math.h): calling it changed this kernel's code
     M3 v3;
     v3.m[0][0] = p.Jxx * dxx * p.Jxx;
     v3.m[1][1] = p.Jyy * dyy * p.Jyy;
@@ -427,6 +309,7 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
     if (a.v_depths) vmc[2] += a.v_depths[idx];  // null: depths unused downstream
 
     // ---- world->camera VJP (transform.py:38-119, 184-297)
+    // mirrors world_to_cam_vjp (proj_math.h): calling it changed this kernel's code
 #pragma unroll
     for (int j = 0; j < 3; ++j)
       vm[j] = k.R.m[0][j] * vmc[0] + k.R.m[1][j] * vmc[1] + k.R.m[2][j] * vmc[2];
@@ -573,52 +456,7 @@ __global__ void __launch_bounds__(256) projection_bwd_kernel(ProjBwdArgs a) {
       a.pose_ws[(size_t)blockIdx.x * 16 + e] = e < 15 ? s : 0.f;
     }
   }
-  if (a.v_viewmats && packed) {
-    // entries are camera-major: a wave spans one camera except at camera
-    // boundaries, where its lanes add their partials one by one
-    const int lane = threadIdx.x & 63;
-    float v[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) v[i * 4 + j] = vR[i][j];
-      v[i * 4 + 3] = vt[i];
-    }
-    const int c0 = __shfl(c, 0, 64);
-    if (__ballot(valid && c != c0) == 0) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) v[e] = wave_sum(v[e]);
-      if (lane == 0)
-        for (int e = 0; e < 12; ++e)
-          if (v[e] != 0.f) atomic_add_f32(a.v_viewmats + c0 * 16 + e, v[e]);
-    } else if (valid) {
-      for (int e = 0; e < 12; ++e)
-        if (v[e] != 0.f) atomic_add_f32(a.v_viewmats + c * 16 + e, v[e]);
-    }
-  } else if (a.v_viewmats) {
-    // block reduction of the 12 viewmat partials: wave butterfly, then LDS
-    __shared__ float red[4][12];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    float v[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) v[i * 4 + j] = vR[i][j];
-      v[i * 4 + 3] = vt[i];
-    }
-#pragma unroll
-    for (int e = 0; e < 12; ++e) v[e] = wave_sum(v[e]);
-    if (lane == 0) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) red[wid][e] = v[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-      float s = 0.f;
-      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w][threadIdx.x];
-      if (s != 0.f) atomic_add_f32(a.v_viewmats + c * 16 + threadIdx.x, s);
-    }
-  }
+  reduce_v_viewmats(a.v_viewmats, packed, valid, c, vR, vt);
 }
 
 }  // namespace gs

@@ -10,49 +10,15 @@
 //
 // All kernels are one lane per (camera, Gaussian) pair, streaming: no LDS
 // beyond the view-matrix reductions.  The grid is (ceil(N/256), C) so the
-// camera parameters are wave-uniform scalar loads.  The camera helpers below
-// (Cam, load_cam, persp and the conic / blur / perspective VJP) restate the
-// ones of projection.hip: that unit's kernels are pinned bit for bit by the
-// training tests and are not touched.
+// camera parameters are wave-uniform scalar loads.  The camera and the pinhole
+// EWA algebra, forward and VJP, are proj_math.h's, shared with projection.hip;
+// this file adds the [N,6] rows, the stages and the other camera models.
 #include "common.h"
+#include "proj_math.h"
 #include "../../include/gsplat_hip.h"
 
 namespace gs {
-
-void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st);
-
 namespace cv {
-
-struct Cam {
-  M3 R;
-  float t[3];
-  float fx, fy, cx, cy;
-};
-
-GS_INLINE void load_K(Cam &k, const float *__restrict__ Ks, int c) {
-  const float *K = Ks + c * 9;
-  k.fx = K[0];
-  k.fy = K[4];
-  k.cx = K[2];
-  k.cy = K[5];
-}
-
-GS_INLINE void load_view(Cam &k, const float *__restrict__ viewmats, int c) {
-  const float *V = viewmats + c * 16;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) k.R.m[i][j] = V[i * 4 + j];
-    k.t[i] = V[i * 4 + 3];
-  }
-}
-
-GS_INLINE Cam load_cam(const float *__restrict__ viewmats, const float *__restrict__ Ks, int c) {
-  Cam k;
-  load_view(k, viewmats, c);
-  load_K(k, Ks, c);
-  return k;
-}
 
 // Symmetric 3x3 from a [N,6] row.  Rows are 24 B: 8-B aligned, three float2.
 GS_INLINE M3 load_covar6(const float *__restrict__ covars, size_t n) {
@@ -68,39 +34,6 @@ GS_INLINE M3 load_covar6(const float *__restrict__ covars, size_t n) {
   return m;
 }
 
-struct ProjOut {
-  float mx, my;             // projected mean
-  float cxx, cxy, cyy;      // 2D covariance (before blur)
-  float Jxx, Jxz, Jyy, Jyz; // Jacobian (clamped screen coordinates)
-  bool clamp_x, clamp_y;
-};
-
-// Pinhole projection with the 15% screen-margin clamp (symmetric covariance).
-GS_INLINE ProjOut persp(float x, float y, float z, const M3 &Cc, const Cam &k, int W, int H) {
-  ProjOut o;
-  float iz = 1.f / z;
-  float marx = 0.15f * (float)W / k.fx;
-  float mary = 0.15f * (float)H / k.fy;
-  float lox = -marx - k.cx / k.fx, hix = marx + ((float)W - k.cx) / k.fx;
-  float loy = -mary - k.cy / k.fy, hiy = mary + ((float)H - k.cy) / k.fy;
-  float sx = x * iz, sy = y * iz;
-  o.clamp_x = (sx < lox) | (sx > hix);
-  o.clamp_y = (sy < loy) | (sy > hiy);
-  sx = fminf(fmaxf(sx, lox), hix);
-  sy = fminf(fmaxf(sy, loy), hiy);
-  o.Jxx = k.fx * iz;
-  o.Jxz = -k.fx * sx * iz;
-  o.Jyy = k.fy * iz;
-  o.Jyz = -k.fy * sy * iz;
-  const float(*c)[3] = Cc.m;
-  o.cxx = o.Jxx * c[0][0] * o.Jxx + 2.f * o.Jxx * c[0][2] * o.Jxz + o.Jxz * c[2][2] * o.Jxz;
-  o.cxy = o.Jxx * (c[0][1] * o.Jyy + c[0][2] * o.Jyz) + o.Jxz * (c[1][2] * o.Jyy + c[2][2] * o.Jyz);
-  o.cyy = o.Jyy * c[1][1] * o.Jyy + 2.f * o.Jyy * c[1][2] * o.Jyz + o.Jyz * c[2][2] * o.Jyz;
-  o.mx = k.fx * x * iz + k.cx;
-  o.my = k.fy * y * iz + k.cy;
-  return o;
-}
-
 // ===================================================== fused, from covars ==
 struct FwdArgs {
   int C, N, W, H;
@@ -114,9 +47,7 @@ struct FwdArgs {
   int64_t *camera_ids, *gaussian_ids;
 };
 
-// MODE 0: dense [C, N] outputs.  MODE 1: count the kept pairs per block.
-// MODE 2: write the kept pairs packed at block_off[block] + rank in block.
-// Culling and outputs are those of projection_fwd_kernel (projection.hip).
+// MODE 0 / 1 / 2: dense outputs, packed count, packed write (ewa_fwd_tail).
 template <int MODE>
 __global__ void __launch_bounds__(256) covar_fwd_kernel(FwdArgs a) {
   const int c = blockIdx.y;
@@ -127,68 +58,7 @@ __global__ void __launch_bounds__(256) covar_fwd_kernel(FwdArgs a) {
   const int n = in ? n_raw : a.N - 1;  // packed modes: every lane reaches the block scan
   const M3 C3 = load_covar6(a.covars, (size_t)n);
   const float *mp = a.means + 3 * (size_t)n;
-  const float m0 = mp[0], m1 = mp[1], m2 = mp[2];
-
-  float mc[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    mc[i] = k.R.m[i][0] * m0 + k.R.m[i][1] * m1 + k.R.m[i][2] * m2 + k.t[i];
-  const M3 Cc = mul(mul(k.R, C3), transpose(k.R));
-
-  const size_t idx = (size_t)c * a.N + n;
-  if (MODE == 0) a.depths[idx] = mc[2];
-  bool keep = in & (mc[2] > a.near_plane) & (mc[2] < a.far_plane);
-
-  ProjOut p = persp(mc[0], mc[1], mc[2], Cc, k, a.W, a.H);
-  const float det0 = p.cxx * p.cyy - p.cxy * p.cxy;
-  const float bxx = p.cxx + a.eps2d, byy = p.cyy + a.eps2d;
-  const float det = bxx * byy - p.cxy * p.cxy;
-  keep &= det > 0.f;
-  const float inv_det = 1.f / det;
-  const float b = 0.5f * (bxx + byy);
-  const float v1 = b + sqrtf(fmaxf(0.01f, b * b - det));
-  const float r = ceilf(3.f * sqrtf(v1));
-  keep &= (r > a.radius_clip) & (p.mx + r > 0.f) & (p.mx - r < (float)a.W) &
-          (p.my + r > 0.f) & (p.my - r < (float)a.H);
-
-  if (MODE == 0) {
-    a.radii[idx] = keep ? (int32_t)r : 0;
-    float2 m2d = keep ? make_float2(p.mx, p.my) : make_float2(0.f, 0.f);
-    *reinterpret_cast<float2 *>(a.means2d + 2 * idx) = m2d;
-    float *cn = a.conics + 3 * idx;
-    cn[0] = keep ? inv_det * byy : 0.f;
-    cn[1] = keep ? -inv_det * p.cxy : 0.f;
-    cn[2] = keep ? inv_det * bxx : 0.f;
-    if (a.comps) a.comps[idx] = keep ? sqrtf(fmaxf(det0 / det, 0.f)) : 0.f;
-    return;
-  }
-  // packed: rank of this pair among the block's kept pairs (wave ballots)
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint64_t m = __ballot(keep);
-  if (lane == 0) wave_cnt[wid] = __popcll(m);
-  __syncthreads();
-  const int64_t blk = (int64_t)c * gridDim.x + blockIdx.x;
-  if (MODE == 1) {
-    if (threadIdx.x == 0) a.block_cnt[blk] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    return;
-  }
-  if (!keep) return;
-  int before = 0;
-  for (int w = 0; w < wid; ++w) before += wave_cnt[w];
-  const int64_t o = a.block_off[blk] + before +
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-  a.camera_ids[o] = c;
-  a.gaussian_ids[o] = n;
-  a.radii[o] = (int32_t)r;
-  *reinterpret_cast<float2 *>(a.means2d + 2 * o) = make_float2(p.mx, p.my);
-  a.depths[o] = mc[2];
-  float *cn = a.conics + 3 * o;
-  cn[0] = inv_det * byy;
-  cn[1] = -inv_det * p.cxy;
-  cn[2] = inv_det * bxx;
-  if (a.comps) a.comps[o] = sqrtf(fmaxf(det0 / det, 0.f));
+  ewa_fwd<MODE>(a, k, c, n, in, mp[0], mp[1], mp[2], C3);
 }
 
 struct BwdArgs {
@@ -216,108 +86,31 @@ GS_INLINE void store_covar6(float *__restrict__ v_covars, size_t row, const floa
 
 __global__ void __launch_bounds__(256) covar_bwd_kernel(BwdArgs a) {
   const bool packed = a.camera_ids != nullptr;
-  int c, n;
-  size_t idx;
-  bool valid;
-  if (packed) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    valid = e < a.nnz;
-    c = valid ? (int)a.camera_ids[e] : 0;
-    n = valid ? (int)a.gaussian_ids[e] : 0;
-    idx = valid ? (size_t)e : 0;
-  } else {
-    c = blockIdx.y;
-    n = blockIdx.x * blockDim.x + threadIdx.x;
-    idx = (size_t)c * a.N + n;
-    valid = (n < a.N) && (a.radii[idx] > 0);
-  }
+  const PairIdx pr = decode_pair(a, packed, blockDim.x);
+  const int c = pr.c, n = pr.n;
+  const size_t idx = pr.idx;
+  const bool valid = pr.valid;
   const Cam k = load_cam(a.viewmats, a.Ks, c);
 
   float vR[3][3] = {{0.f}}, vt[3] = {0.f, 0.f, 0.f};
   float vm[3] = {0.f, 0.f, 0.f}, vc6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   if (valid) {
-    // ---- conic inverse VJP; v_conic_xy halved
-    const float *cn = a.conics + 3 * idx;
-    const float ca = cn[0], cb = cn[1], cc = cn[2];
-    const float *vc = a.v_conics + 3 * idx;
-    const float va = vc[0], vb = 0.5f * vc[1], vcc = vc[2];
-    float dxx = -(ca * va * ca + cb * vcc * cb + 2.f * cb * vb * ca);
-    float dxy = -(ca * vb * cc + cb * vb * cb + cb * vcc * cc + ca * va * cb);
-    float dyy = -(cb * va * cb + cc * vcc * cc + 2.f * cc * vb * cb);
-    if (a.comps) {  // blur VJP
-      const float cp = a.comps[idx], vcp = a.v_comps[idx];
-      const float det_i = ca * cc - cb * cb;
-      const float Da = 0.5f * vcp / (cp + 1e-6f);
-      const float oma = 1.f - cp * cp;
-      dxx += Da * (oma * ca - a.eps2d * det_i);
-      dxy += Da * (oma * cb);
-      dyy += Da * (oma * cc - a.eps2d * det_i);
-    }
+    const Sym2 d = conic_blur_vjp(a, idx);
     // ---- recompute the forward intermediates
     const M3 C3 = load_covar6(a.covars, (size_t)n);
     const float *mp = a.means + 3 * (size_t)n;
     const float m[3] = {mp[0], mp[1], mp[2]};
     float mc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      mc[i] = k.R.m[i][0] * m[0] + k.R.m[i][1] * m[1] + k.R.m[i][2] * m[2] + k.t[i];
+    world_to_cam_mean(k, m[0], m[1], m[2], mc);
     const M3 Cc = mul(mul(k.R, C3), transpose(k.R));
     const ProjOut p = persp(mc[0], mc[1], mc[2], Cc, k, a.W, a.H);
-    const float iz = 1.f / mc[2];
 
-    // ---- perspective VJP
     M3 v3;
-    v3.m[0][0] = p.Jxx * dxx * p.Jxx;
-    v3.m[1][1] = p.Jyy * dyy * p.Jyy;
-    v3.m[2][2] = p.Jxz * dxx * p.Jxz + p.Jyz * dyy * p.Jyz + 2.f * p.Jyz * dxy * p.Jxz;
-    v3.m[0][1] = v3.m[1][0] = p.Jxx * dxy * p.Jyy;
-    v3.m[0][2] = v3.m[2][0] = p.Jxx * dxx * p.Jxz + p.Jxx * dxy * p.Jyz;
-    v3.m[1][2] = v3.m[2][1] = p.Jyy * dxy * p.Jxz + p.Jyy * dyy * p.Jyz;
-
-    const float vm2x = a.v_means2d[2 * idx], vm2y = a.v_means2d[2 * idx + 1];
     float vmc[3];
-    // means2d is the unclamped projection, so its z-gradient takes the
-    // unclamped x / z, y / z (gsplat/cuda/include/Utils.cuh:521-528; only the
-    // Jacobian of the covariance is clamped)
-    vmc[0] = p.Jxx * vm2x;
-    vmc[1] = p.Jyy * vm2y;
-    vmc[2] = -(k.fx * mc[0] * vm2x + k.fy * mc[1] * vm2y) * (iz * iz);
-    const float(*cm)[3] = Cc.m;
-    const float Jc_xx = p.Jxx * cm[0][0] + p.Jxz * cm[0][2];
-    const float Jc_xy = p.Jxx * cm[0][1] + p.Jxz * cm[1][2];
-    const float Jc_xz = p.Jxx * cm[0][2] + p.Jxz * cm[2][2];
-    const float Jc_yx = p.Jyy * cm[0][1] + p.Jyz * cm[0][2];
-    const float Jc_yy = p.Jyy * cm[1][1] + p.Jyz * cm[1][2];
-    const float Jc_yz = p.Jyy * cm[1][2] + p.Jyz * cm[2][2];
-    const float vJxx = 2.f * (dxx * Jc_xx + dxy * Jc_yx);
-    const float vJxz = 2.f * (dxx * Jc_xz + dxy * Jc_yz);
-    const float vJyy = 2.f * (dxy * Jc_xy + dyy * Jc_yy);
-    const float vJyz = 2.f * (dxy * Jc_xz + dyy * Jc_yz);
-    const float iz2 = iz * iz;
-    vmc[0] += p.clamp_x ? 0.f : -vJxz * k.fx * iz2;
-    vmc[1] += p.clamp_y ? 0.f : -vJyz * k.fy * iz2;
-    float tmp = vJxx * p.Jxx + vJyy * p.Jyy + 2.f * (vJxz * p.Jxz + vJyz * p.Jyz);
-    tmp -= p.clamp_x ? vJxz * p.Jxz : 0.f;
-    tmp -= p.clamp_y ? vJyz * p.Jyz : 0.f;
-    vmc[2] -= iz * tmp;
+    persp_vjp<false>(p, k, mc, Cc, d, a.v_means2d[2 * idx], a.v_means2d[2 * idx + 1], v3, vmc);
     if (a.v_depths) vmc[2] += a.v_depths[idx];  // null: depths unused downstream
-
-    // ---- world->camera VJP
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      vm[j] = k.R.m[0][j] * vmc[0] + k.R.m[1][j] * vmc[1] + k.R.m[2][j] * vmc[2];
-    const M3 vSR = mul(v3, k.R);
-    const M3 vC3 = mul(transpose(k.R), vSR);
-    if (a.v_viewmats) {
-      const M3 vRc = mul(vSR, C3);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        vt[i] = vmc[i];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) vR[i][j] = vmc[i] * m[j] + 2.f * vRc.m[i][j];
-      }
-    }
+    const M3 vC3 = world_to_cam_vjp(k, C3, m, v3, vmc, a.v_viewmats != nullptr, vm, vR, vt);
     // ---- upper triangle: diagonal as it is, off-diagonal v[i][j] + v[j][i]
     vc6[0] = vC3.m[0][0];
     vc6[1] = vC3.m[0][1] + vC3.m[1][0];
@@ -345,53 +138,7 @@ __global__ void __launch_bounds__(256) covar_bwd_kernel(BwdArgs a) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) atomic_add_f32(a.v_covars + 6 * (size_t)n + j, vc6[j]);
   }
-
-  if (a.v_viewmats && packed) {
-    // entries are camera-major: a wave spans one camera except at camera
-    // boundaries, where its lanes add their partials one by one
-    const int lane = threadIdx.x & 63;
-    float v[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) v[i * 4 + j] = vR[i][j];
-      v[i * 4 + 3] = vt[i];
-    }
-    const int c0 = __shfl(c, 0, 64);
-    if (__ballot(valid && c != c0) == 0) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) v[e] = wave_sum(v[e]);
-      if (lane == 0)
-        for (int e = 0; e < 12; ++e)
-          if (v[e] != 0.f) atomic_add_f32(a.v_viewmats + c0 * 16 + e, v[e]);
-    } else if (valid) {
-      for (int e = 0; e < 12; ++e)
-        if (v[e] != 0.f) atomic_add_f32(a.v_viewmats + c * 16 + e, v[e]);
-    }
-  } else if (a.v_viewmats) {
-    // block reduction of the 12 viewmat partials: wave butterfly, then LDS
-    __shared__ float red[4][12];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    float v[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) v[i * 4 + j] = vR[i][j];
-      v[i * 4 + 3] = vt[i];
-    }
-#pragma unroll
-    for (int e = 0; e < 12; ++e) v[e] = wave_sum(v[e]);
-    if (lane == 0) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) red[wid][e] = v[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-      float s = 0.f;
-      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w][threadIdx.x];
-      if (s != 0.f) atomic_add_f32(a.v_viewmats + c * 16 + threadIdx.x, s);
-    }
-  }
+  reduce_v_viewmats(a.v_viewmats, packed, valid, c, vR, vt);
 }
 
 // ========================================================== world_to_cam ==
@@ -584,26 +331,6 @@ GS_INLINE Fish fisheye_scalars(float xf, float yf, float zf) {
     f.Q1 = (float)Q1;
   }
   return f;
-}
-
-struct PinClamp {
-  float iz, sx, sy;
-  bool cx, cy;
-};
-
-GS_INLINE PinClamp pin_clamp(float x, float y, float z, const Cam &k, int W, int H) {
-  PinClamp p;
-  p.iz = 1.f / z;
-  const float marx = 0.15f * (float)W / k.fx;
-  const float mary = 0.15f * (float)H / k.fy;
-  const float lox = -marx - k.cx / k.fx, hix = marx + ((float)W - k.cx) / k.fx;
-  const float loy = -mary - k.cy / k.fy, hiy = mary + ((float)H - k.cy) / k.fy;
-  const float sx = x * p.iz, sy = y * p.iz;
-  p.cx = (sx < lox) | (sx > hix);
-  p.cy = (sy < loy) | (sy > hiy);
-  p.sx = fminf(fmaxf(sx, lox), hix);
-  p.sy = fminf(fmaxf(sy, loy), hiy);
-  return p;
 }
 
 GS_INLINE Jac jac_pinhole(float x, float y, const PinClamp &p, const Cam &k) {

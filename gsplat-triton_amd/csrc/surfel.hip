@@ -26,6 +26,7 @@
 //    densification gradient.
 #include "common.h"
 #include "geom_adam.h"
+#include "proj_math.h"  // launch_packed_scan; Cam here is surfel::Cam
 #include "wave_ops.h"
 #include "surfel_cull.h"
 #include "../../include/gsplat_hip.h"
@@ -1944,10 +1945,6 @@ extern "C" int gsplat_hip_projection_2dgs_bwd_adam(
 // projection_2dgs_packed_fwd (gsplat/cuda/csrc/Projection2DGSPacked.cu:17-270):
 // a counting pass, a scan of the per-block counts and a pass that recomputes
 // and writes the kept (camera, surfel) pairs in (camera, surfel) order.
-namespace gs {
-void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st);
-}
-
 extern "C" int64_t gsplat_hip_projection_2dgs_packed_workspace_bytes(int C, int N) {
   const int64_t nb = (int64_t)C * ((N + 255) / 256);
   return (nb + 1) * (int64_t)sizeof(int64_t);

@@ -12,6 +12,8 @@ Gaussians, one 1920x1080 camera), HIP events, in one process:
            user without these kernels would run it.
   models:  proj alone, pinhole / ortho / fisheye, forward and
            forward+backward.
+  packed:  the packed forward (count, scan, write) of both fused paths; not
+           part of `all`, it only gives rocprofv3 the packed kernels to time.
 
 Every figure is event time per Python call: the larger of the host's issue
 time (wrapper, allocations, launches) and the GPU's time, not kernel time.
@@ -19,7 +21,7 @@ Prints one JSON line per measurement and appends them to
 profiles/covars/covar_proj_bench.txt (--out).  For kernel times run under
 `rocprofv3 --kernel-trace --stats` (no counters in the same run).
 
-    python tools/covar_proj_bench.py [--part fused|stages|models|all] [--iters 300]
+    python tools/covar_proj_bench.py [--part fused|stages|models|packed|all] [--iters 300]
 """
 
 import argparse
@@ -200,10 +202,24 @@ def part_models(iters):
         emit(row)
 
 
+def part_packed(iters):
+    import gsplat_hip
+    means, quats, scales, vm, K = scene()
+    covars = gsplat_hip.quat_scale_to_covar_preci(quats, scales, compute_preci=False, triu=True)[0]
+    kw = dict(eps2d=0.3, near_plane=0.01, far_plane=1e10, radius_clip=0.0, packed=True)
+    us = {"fwd_quats_scales": timed(lambda: gsplat_hip.fully_fused_projection(
+              means, None, quats, scales, vm, K, W, H, **kw), iters),
+          "fwd_covars": timed(lambda: gsplat_hip.fully_fused_projection(
+              means, covars, None, None, vm, K, W, H, **kw), iters)}
+    emit({"part": "packed", "gaussians": means.shape[0], "iters": iters,
+          **{k + "_us": round(v, 2) for k, v in us.items()},
+          "note": "event time per call: two kernels, the scan, a host read of nnz"})
+
+
 def main():
     global _OUT
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=("fused", "stages", "models", "all"))
+    ap.add_argument("--part", default="all", choices=("fused", "stages", "models", "packed", "all"))
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "covars",
                                                   "covar_proj_bench.txt"))
@@ -218,6 +234,8 @@ def main():
         part_stages(args.iters)
     if args.part in ("models", "all"):
         part_models(args.iters)
+    if args.part == "packed":
+        part_packed(args.iters)
 
 
 if __name__ == "__main__":
