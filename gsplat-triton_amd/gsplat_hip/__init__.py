@@ -26,6 +26,7 @@ from .appearance import appearance_colors
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
 from .compression import PngCompression
 from .depth_loss import sparse_depth_loss
+from .io import load_ply, save_ply
 from .losses import geometry_loss_2dgs
 from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
@@ -63,5 +64,7 @@ __all__ = [
     "accumulate_2dgs",
     "undistort_images",
     "remap_bilinear",
+    "save_ply",
+    "load_ply",
 ]
 __version__ = "0.1.0"

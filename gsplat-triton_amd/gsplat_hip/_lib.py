@@ -221,6 +221,10 @@ _SIGS = {
     "gsplat_hip_undistort_u8_f32": (_i32, [_i32, _i32, _i32, _p] + [_d] * 12
                                     + [_i32, _i32, _i32, _i32, _i32, _f, _p, _p]),
     "gsplat_hip_remap_u8_f32": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _i32, _f, _p, _p]),
+    "gsplat_hip_ply_workspace_bytes": (_i64, [_i64]),
+    "gsplat_hip_ply_count": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_ply_pack": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_ply_unpack": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_watchdog_arm": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
     "gsplat_hip_watchdog_beat": (_i32, [ctypes.c_char_p]),
     "gsplat_hip_watchdog_set_fallback": (_i32, [_i32, ctypes.c_char_p, _i32]),

@@ -276,6 +276,7 @@ _REFUSALS = {
     "normal_loss / dist_loss": ("the one-GPU dense 2DGS trainer only",
                                 ("packed", "sparse_grad") + _MANY),
     "compression": ("one-GPU trainers only", _MANY),
+    "checkpoint": ("one-GPU trainers only", _MANY),
 }
 
 
@@ -1488,6 +1489,44 @@ class Trainer:
             os.path.getsize(os.path.join(compress_dir, f)) for f in os.listdir(compress_dir)
             if os.path.isfile(os.path.join(compress_dir, f)))
         return out
+
+    # ---------------------------------------------------------- persistence
+    def save_checkpoint(self, path, step: int):
+        """simple_trainer.py save_steps (:734-747): one torch.save file with the
+        reference's keys ("step", "splats", "pose_adjust", "app_module"), which
+        its `ckpt=` reads, plus a "gsplat_hip" block with everything else the
+        next step reads (checkpoint.py), so load_checkpoint resumes the run
+        exactly.  `step`: the index of the last completed step.  Calls sync()
+        first; the trainer and a captured step are left untouched."""
+        from . import checkpoint
+        checkpoint.save(self, path, step)
+
+    def load_checkpoint(self, paths, resume: bool = True) -> int:
+        """Returns the checkpoint's step.  resume=True (one file written by
+        save_checkpoint): the configuration fingerprint must match (ValueError
+        naming every field that differs); parameters, moments, step counts, side
+        optimizers, statistics and generator state are restored, and the
+        caller continues with step(step + 1).  A list of files, resume=False,
+        or a file of the reference trainer: its evaluation path
+        (simple_trainer.py:1055-1064) -- the files' Gaussians concatenated,
+        pose_adjust / app_module from the first, zero moments and step counts,
+        fresh statistics."""
+        from . import checkpoint
+        return checkpoint.load(self, paths, resume)
+
+    def load_splats(self, splats):
+        """load_checkpoint's evaluation path for a dict name -> tensor, e.g.
+        from gsplat_hip.load_ply or PngCompression.decompress."""
+        from . import checkpoint
+        checkpoint.load_splats(self, splats)
+
+    def save_ply(self, path, sh_degree: Optional[int] = None):
+        """simple_trainer.py save_ply / ply_steps (:748-765): gsplat_hip.save_ply
+        of the synced parameters; app_opt: the colours baked at the zero
+        embedding and zero view direction at `sh_degree` (the reference passes
+        the step's sh_degree_to_use; None: the trainer's sh_degree)."""
+        from . import checkpoint
+        return checkpoint.save_ply(self, path, sh_degree)
 
     # ------------------------------------------------------------ strategy
     def post_step(self, it: int, replayed: bool = False):

@@ -65,7 +65,8 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_app_colors_fwd / _bwd, gsplat_hip_app_reduce_adam and
  *     gsplat_hip_app_workspace_bytes (appearance optimisation);
  *     gsplat_hip_kmeans_l1_assign, gsplat_hip_kmeans_update and
- *     gsplat_hip_kmeans_update_workspace_bytes (splat compression). */
+ *     gsplat_hip_kmeans_update_workspace_bytes (splat compression);
+ *     gsplat_hip_ply_count / _pack / _unpack / _workspace_bytes (PLY rows). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1370,6 +1371,40 @@ int gsplat_hip_undistort_u8_f32(int B, int H, int W, const uint8_t *images, doub
 int gsplat_hip_remap_u8_f32(int B, int H, int W, const uint8_t *images, const float *mapx,
                             const float *mapy, int w, int h, float scale, float *out,
                             void *stream);
+
+/* ---------------------------------------------------------------------------
+ * PLY rows in the INRIA layout (ABI 38, new entries only; csrc/ply.hip): the
+ * vertex rows gsplat/utils.py:10-98 save_ply writes one struct.pack at a time,
+ * and the way back.  A row is F = 17 + 3 K1 little-endian floats,
+ *   x y z | nx ny nz (0) | f_dc_0..2 | f_rest_0..3K1-1 | opacity | scale_0..2 | rot_0..3
+ * with f_rest_j = shN[n, j % K1, j / K1] (channel-major), K1 = K - 1 in 0..24.
+ * With `colors` [n,3] (then K1 = 0, sh0 / shN are not read):
+ *   f_dc_j = (colors[n,j] - 0.5f) / 0.2820947917738781f, an fp32 subtract and a
+ *   correctly rounded fp32 divide.
+ * A source row is kept when every float of its file row is finite; the kept
+ * rows keep their order.  Inputs: means[n,3] scales[n,3] quats[n,4]
+ * opacities[n] sh0[n,1,3] shN[n,K1,3], contiguous float32.  n <= 2^31 per call.
+ * No atomics: bit-identical between calls.
+ *   _workspace_bytes: of uninitialised memory, 8-B aligned, for n rows.
+ *   _count:  fills the workspace (per-workgroup offsets of the kept rows, a
+ *            validity byte per row) and n_valid_device[0] (8-B aligned).
+ *   _pack:   after _count with the same arguments: rows[n_valid, F].
+ *   _unpack: rows[n, F] (F floats per file row, any F >= 14 + 3 K1) back to
+ *            the parameter arrays; cols (device int32 [14 + 3 K1]) names the
+ *            column of x y z, f_dc_0..2, f_rest_0.., opacity, scale_0..2,
+ *            rot_0..3 in that order, each in [0, F): the caller checks them. */
+int64_t gsplat_hip_ply_workspace_bytes(int64_t n);
+int gsplat_hip_ply_count(int64_t n, int K1, const float *means, const float *scales,
+                         const float *quats, const float *opacities, const float *sh0,
+                         const float *shN, const float *colors, void *workspace,
+                         int64_t *n_valid_device, void *stream);
+int gsplat_hip_ply_pack(int64_t n, int K1, const float *means, const float *scales,
+                        const float *quats, const float *opacities, const float *sh0,
+                        const float *shN, const float *colors, const void *workspace,
+                        float *rows, void *stream);
+int gsplat_hip_ply_unpack(int64_t n, int K1, int F, const float *rows, const int32_t *cols,
+                          float *means, float *scales, float *quats, float *opacities,
+                          float *sh0, float *shN, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
