@@ -496,250 +496,24 @@ __global__ void __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(
 fused_kernel(int B, int H, int W, const float *__restrict__ x,
              const float *__restrict__ y, const int64_t *__restrict__ y_index, float cs, float cl,
              float *__restrict__ grad, float *__restrict__ partials) {
-  static_assert(C % CPW == 0, "channel groups");
-  constexpr int CG = C / CPW;
-  __shared__ __attribute__((aligned(16))) char lds[kFusedLds];
-  __shared__ float red[2][kFThreads / 64];
-  f2v(*s_xy)[SX] = reinterpret_cast<f2v(*)[SX]>(lds);
-  f2v(*hA)[SH] = reinterpret_cast<f2v(*)[SH]>(lds + kOffA);
-  f2v(*hB)[SH] = reinterpret_cast<f2v(*)[SH]>(lds + kOffB);
-  float(*hC)[SH] = reinterpret_cast<float(*)[SH]>(lds + kOffC);
-  f2v(*m01)[SH] = reinterpret_cast<f2v(*)[SH]>(lds);
-  float(*m2)[SH] = reinterpret_cast<float(*)[SH]>(lds + FM * SH * 8);
-  f2v(*g01)[SG] = reinterpret_cast<f2v(*)[SG]>(lds + kOffA);
-  float(*g2)[SG] = reinterpret_cast<float(*)[SG]>(lds + kOffA + FM * SG * 8);
+#define GS_FUSED_MASKED 0
+#include "ssim_fused_body.h"
+#undef GS_FUSED_MASKED
+}
 
-  const int Hm = H - 2 * R, Wm = W - 2 * R;
-  const int tx = (W + FT - 1) / FT, ty = (H + FT - 1) / FT, nt = tx * ty, ntc = nt * CG;
-  // XCD-aware: workgroup L runs on XCD L % 8; each XCD takes a contiguous
-  // run of (tile, channel group)s so neighbouring windows' shared apron rows
-  // (and a tile's other channel groups) hit its L2
-  const int per = (ntc + 7) / 8, L = blockIdx.x;
-  const int b = L / (8 * per), q = L - b * 8 * per;
-  const int tc = (q & 7) * per + (q >> 3);
-  if (b >= B || tc >= ntc) return;
-  const int t = tc / CG, cg = tc - t * CG;
-  if (y_index) y += y_index[0] * ((int64_t)B * H * W * C);  // image y_index of a stack
-  const int qi0 = (t / tx) * FT, qj0 = (t % tx) * FT;  // image tile origin
-  const int ri0 = qi0 - 2 * R, rj0 = qj0 - 2 * R;       // window origin (image coords)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  // window loads of one channel: lane = window column, wave w = rows w, w+8,
-  // ...; clamped addresses (unconditional loads), zeroed outside the image
-  // (row pointers are wave-uniform: saddr + one 32-bit lane offset per load)
-  // x (the render, and its gradient) has XS >= C floats per pixel (an RGB+D
-  // render read in place: XS = 4, C = 3); y has C
-  const int colc = min(max(rj0 + lane, 0), W - 1);
-  const uint32_t lox = (uint32_t)(colc * XS), loy = (uint32_t)(colc * C);
-  const bool col_ok = lane < FI && rj0 + lane >= 0 && rj0 + lane < W;
-  const float *xb = x + (int64_t)b * H * W * XS, *yb = y + (int64_t)b * H * W * C;
-  float vx[kFRows], vy[kFRows];
-  auto load = [&](int c) {
-#pragma unroll
-    for (int k = 0; k < kFRows; ++k) {
-      const int64_t row = (int64_t)min(max(ri0 + w8 + 8 * k, 0), H - 1) * W;
-      vx[k] = (xb + row * XS)[lox + c];
-      vy[k] = (yb + row * C)[loy + c];
-    }
-  };
-  float lsum = 0.f, ssum = 0.f;
-  // backward vertical pass mapping: column gc, image rows 2 gr, 2 gr + 1
-  const int gc = tid & 31, gr = tid >> 5;
-  // the loaded window into s_xy (+ its L1 over the tile's own pixels, window
-  // rows / cols 2R .. 2R+31)
-  auto stage = [&]() {
-#pragma unroll
-    for (int k = 0; k < kFRows; ++k) {
-      const int r = w8 + 8 * k, gi = ri0 + r;
-      const bool ok = col_ok && r < FI && gi >= 0 && gi < H;
-      const float a = ok ? vx[k] : 0.f, bb = ok ? vy[k] : 0.f;
-      if (r < FI && lane < FI) s_xy[r][lane] = f2v{a, bb};
-      if (r >= 2 * R && r < 2 * R + FT && lane >= 2 * R && lane < 2 * R + FT)
-        lsum += fabsf(a - bb);
-    }
-  };
-  // The next channel's window is loaded while pass C1 runs (its latency
-  // hidden behind C1) and staged while C2 runs: s_xy's last readers of this
-  // channel (pass C1, through m01 / m2) are behind C1's barrier, and this
-  // channel's own pixels (px0 / px1) were read into registers before pass A.
-  const int c_end = cg * CPW + CPW;
-  load(cg * CPW);
-  stage();
-  __syncthreads();
-#pragma nounroll
-  for (int c = cg * CPW; c < c_end; ++c) {
-    const f2v px0 = s_xy[2 * R + 2 * gr][2 * R + gc], px1 = s_xy[2 * R + 2 * gr + 1][2 * R + gc];
-    // ---- A: horizontal blur of the statistics, FI rows x FM columns
-    static_assert(FM % kHA == 0 && FT % kHC == 0, "pass A / C1 blocking");
-    for (int idx = tid; idx < FI * (FM / kHA); idx += kFThreads) {
-      const int jg = idx / FI, r = idx - jg * FI, j0 = jg * kHA;
-      f2v v[K + kHA - 1], sq[K + kHA - 1];
-      float xy[K + kHA - 1];
-#pragma unroll
-      for (int i = 0; i < K + kHA - 1; ++i) {
-        v[i] = s_xy[r][j0 + i];
-        sq[i] = v[i] * v[i];
-        xy[i] = v[i].x * v[i].y;
-      }
-#pragma unroll
-      for (int o = 0; o < kHA; ++o) {
-        f2v a = {0.f, 0.f}, bb = {0.f, 0.f};
-        float cc = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const float g = kG[k];
-          a = __builtin_elementwise_fma(f2v{g, g}, v[o + k], a);
-          bb = __builtin_elementwise_fma(f2v{g, g}, sq[o + k], bb);
-          cc = __builtin_fmaf(g, xy[o + k], cc);
-        }
-        hA[r][j0 + o] = a;
-        hB[r][j0 + o] = bb;
-        hC[r][j0 + o] = cc;
-      }
-    }
-    __syncthreads();
-    // ---- B: vertical blur -> the partials of map pixels (local rows / cols
-    // 0..FM-1 = map coords ri0.., rj0..; zero outside the valid map), into s_xy
-    constexpr int kItems = (FM + BR - 1) / BR * FM;
-    for (int it = tid; it < kItems; it += kFThreads) {
-      const int mg = it / FM, mc = it - mg * FM;
-      f2v oa[BR], ob[BR];
-      float oc[BR];
-#pragma unroll
-      for (int j = 0; j < BR; ++j) {
-        oa[j] = f2v{0.f, 0.f};
-        ob[j] = f2v{0.f, 0.f};
-        oc[j] = 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < K + BR - 1; ++i) {
-        const int r = min(BR * mg + i, FI - 1);  // rows past FI only feed discarded outputs
-        const f2v a = hA[r][mc], bb = hB[r][mc];
-        const float cc = hC[r][mc];
-#pragma unroll
-        for (int j = 0; j < BR; ++j) {
-          const int k = i - j;
-          if (k >= 0 && k < K) {
-            const float g = kG[k];
-            oa[j] = __builtin_elementwise_fma(f2v{g, g}, a, oa[j]);
-            ob[j] = __builtin_elementwise_fma(f2v{g, g}, bb, ob[j]);
-            oc[j] = __builtin_fmaf(g, cc, oc[j]);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < BR; ++j) {
-        const int mr = BR * mg + j, pi = ri0 + mr, pj = rj0 + mc;
-        float p0 = 0.f, p1 = 0.f, p2 = 0.f;
-        if (pi >= 0 && pi < Hm && pj >= 0 && pj < Wm) {
-          const float u1 = oa[j].x, u2 = oa[j].y;
-          const float s11 = ob[j].x - u1 * u1, s22 = ob[j].y - u2 * u2, s12 = oc[j] - u1 * u2;
-          const float A1 = 2.f * u1 * u2 + C1, A2 = 2.f * s12 + C2;
-          const float B1 = u1 * u1 + u2 * u2 + C1, B2 = s11 + s22 + C2;
-          const float inv = 1.f / (B1 * B2);
-          const float sv = A1 * A2 * inv;
-          if (mr >= 2 * R && mr < FM && mc >= 2 * R) ssum += sv;  // the tile's own map pixels
-          const float dN = 2.f * u2 * (A2 - A1), dD = 2.f * u1 * (B2 - B1);
-          p0 = (dN - sv * dD) * inv;
-          p1 = -sv * B1 * inv;
-          p2 = 2.f * A1 * inv;
-        }
-        if (mr < FM) {
-          m01[mr][mc] = f2v{p0, p1};
-          m2[mr][mc] = p2;
-        }
-      }
-    }
-    __syncthreads();
-    const bool more = c + 1 < c_end;
-    if (more) load(c + 1);
-    // ---- C1: horizontal blur of the partials, FM rows x FT columns (the
-    // adjoint of the valid correlation: full correlation with the symmetric
-    // kernel, see bwd_kernel), into hA
-    for (int idx = tid; idx < FM * (FT / kHC); idx += kFThreads) {
-      const int jg = idx / FM, r = idx - jg * FM, j0 = jg * kHC;
-      f2v v[K + kHC - 1];
-      float w[K + kHC - 1];
-#pragma unroll
-      for (int i = 0; i < K + kHC - 1; ++i) {
-        v[i] = m01[r][j0 + i];
-        w[i] = m2[r][j0 + i];
-      }
-#pragma unroll
-      for (int o = 0; o < kHC; ++o) {
-        f2v a = {0.f, 0.f};
-        float cc = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const float g = kG[k];
-          a = __builtin_elementwise_fma(f2v{g, g}, v[o + k], a);
-          cc = __builtin_fmaf(g, w[o + k], cc);
-        }
-        g01[r][j0 + o] = a;
-        g2[r][j0 + o] = cc;
-      }
-    }
-    __syncthreads();
-    if (more) stage();  // the next channel's window (s_xy is free: see above)
-    // ---- C2: vertical blur onto the tile pixels, gradient out.  (The next
-    // channel's pass A rewrites hA, which C2 reads, only after the barrier
-    // below.)
-    {
-      f2v oa[2] = {f2v{0.f, 0.f}, f2v{0.f, 0.f}};
-      float oc[2] = {0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < K + 1; ++i) {
-        const int r = 2 * gr + i;
-        const f2v a = g01[r][gc];
-        const float cc = g2[r][gc];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int k = i - j;
-          if (k >= 0 && k < K) {
-            const float g = kG[k];
-            oa[j] = __builtin_elementwise_fma(f2v{g, g}, a, oa[j]);
-            oc[j] = __builtin_fmaf(g, cc, oc[j]);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int qi = qi0 + 2 * gr + j, qj = qj0 + gc;
-        const f2v v = j ? px1 : px0;
-        const float d = v.x - v.y;
-        const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        if (qi < H && qj < W)
-          grad[(((int64_t)b * H + qi) * W + qj) * XS + c] =
-              cs * (oa[j].x + 2.f * v.x * oa[j].y + v.y * oc[j]) + cl * sgn;
-      }
-    }
-    if (more) __syncthreads();  // the staged window, and C2's reads of hA done
-  }
-  if (XS > C && cg == CG - 1) {  // the render's other channels: no loss term, zero gradient
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int qi = qi0 + 2 * gr + j, qj = qj0 + gc;
-      if (qi < H && qj < W)
-        for (int e = C; e < XS; ++e) grad[(((int64_t)b * H + qi) * W + qj) * XS + e] = 0.f;
-    }
-  }
-  ssum = wave_sum(ssum);
-  lsum = wave_sum(lsum);
-  if (lane == 0) {
-    red[0][tid >> 6] = ssum;
-    red[1][tid >> 6] = lsum;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float s = 0.f, l = 0.f;
-    for (int w = 0; w < kFThreads / 64; ++w) {
-      s += red[0][w];
-      l += red[1][w];
-    }
-    partials[2 * ((int64_t)b * ntc + tc)] = s;
-    partials[2 * ((int64_t)b * ntc + tc) + 1] = l;
-  }
+// fused_kernel on the masked render over a background (ssim_fused_body.h);
+// all channels of a tile in one workgroup
+template <int C, int BR>
+__global__ void __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(4)))
+fused_masked_kernel(int B, int H, int W, const float *__restrict__ x,
+                    const float *__restrict__ y, const int64_t *__restrict__ y_index, float cs,
+                    float cl, float *__restrict__ grad, float *__restrict__ partials,
+                    const uint8_t *__restrict__ mask, const float *__restrict__ alpha,
+                    const float *__restrict__ bkgd, float *__restrict__ grad_alpha) {
+  constexpr int CPW = C, XS = C;
+#define GS_FUSED_MASKED 1
+#include "ssim_fused_body.h"
+#undef GS_FUSED_MASKED
 }
 
 // grad = g_loss[0] * unit (float4 where aligned)
@@ -937,5 +711,73 @@ extern "C" int gsplat_hip_l1_ssim_loss_fused_bwd(int64_t n, const float *grad_un
   hipLaunchKernelGGL(ssim::fused_scale_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      (hipStream_t)stream, n, grad_unit, g_loss, grad_img1);
   GS_CHECK_LAUNCH("l1_ssim_loss_fused_bwd");
+  return 0;
+}
+
+// ---- the fused loss on the masked / composited render (ssim::fused_masked_kernel)
+extern "C" int gsplat_hip_l1_ssim_loss_masked_fwd(int B, int H, int W, int C, const float *img1,
+                                                  const float *img2, const int64_t *img2_index,
+                                                  const uint8_t *mask, const float *alpha,
+                                                  const float *bkgd, float lam, float *out,
+                                                  float *grad_unit, float *grad_alpha_unit,
+                                                  void *workspace, float *loss_ring,
+                                                  int64_t ring_len, const int64_t *seq_device,
+                                                  void *stream) {
+  GS_REQUIRE(B > 0 && H > 10 && W > 10,
+             "l1_ssim_loss_masked_fwd: images must be larger than the 11x11 window (got %dx%d)", H,
+             W);
+  GS_REQUIRE(C == 1 || C == 3, "l1_ssim_loss_masked_fwd: C must be 1 or 3 (got %d)", C);
+  GS_REQUIRE(out != nullptr && grad_unit != nullptr, "l1_ssim_loss_masked_fwd: null output");
+  GS_REQUIRE(bkgd == nullptr || (alpha != nullptr && grad_alpha_unit != nullptr),
+             "l1_ssim_loss_masked_fwd: bkgd needs alpha and grad_alpha_unit");
+  GS_REQUIRE(loss_ring == nullptr || (seq_device != nullptr && ring_len > 0),
+             "l1_ssim_loss_masked_fwd: a loss ring needs its step counter and length");
+  hipStream_t st = (hipStream_t)stream;
+  float *partials = reinterpret_cast<float *>(workspace);
+  const int64_t nt = fused_tiles(H, W), per = (nt + 7) / 8;
+  const dim3 grid((unsigned)(B * 8 * per));
+  const float cs = -lam / n_map(B, H, W, C), cl = (1.f - lam) / n_img(B, H, W, C);
+  GS_REQUIRE((int64_t)H * W * C < ((int64_t)1 << 31),
+             "l1_ssim_loss_masked_fwd: an image of %dx%dx%d floats exceeds the kernel's 32-bit "
+             "pixel offsets", H, W, C);
+  // map rows per pass-B item as in the plain loss (4 for RGB, 2 for C = 1):
+  // the same pass B, so that with every pixel valid and no background the
+  // result is the plain loss's bit for bit; no scratch at 128 VGPRs
+  // (profiles/masked_loss/README.md)
+  if (C == 3) {
+    hipLaunchKernelGGL((ssim::fused_masked_kernel<3, 4>), grid, dim3(ssim::kFThreads), 0, st, B, H,
+                       W, img1, img2, img2_index, cs, cl, grad_unit, partials, mask, alpha, bkgd,
+                       grad_alpha_unit);
+  } else {
+    hipLaunchKernelGGL((ssim::fused_masked_kernel<1, 2>), grid, dim3(ssim::kFThreads), 0, st, B, H,
+                       W, img1, img2, img2_index, cs, cl, grad_unit, partials, mask, alpha, bkgd,
+                       grad_alpha_unit);
+  }
+  hipLaunchKernelGGL(ssim::reduce_partials_kernel, dim3(1), dim3(1024), 0, st, (int)(B * nt),
+                     partials, nullptr, out, lam, n_map(B, H, W, C), n_img(B, H, W, C), loss_ring,
+                     ring_len, seq_device);
+  GS_CHECK_LAUNCH("l1_ssim_loss_masked_fwd");
+  return 0;
+}
+
+extern "C" int gsplat_hip_l1_ssim_loss_masked_bwd(int64_t n, const float *grad_unit,
+                                                  int64_t n_alpha, const float *grad_alpha_unit,
+                                                  const float *g_loss, float *grad_img1,
+                                                  float *grad_alpha, void *stream) {
+  GS_REQUIRE(n >= 0 && n_alpha >= 0, "l1_ssim_loss_masked_bwd: negative count");
+  GS_REQUIRE(n_alpha == 0 || (grad_alpha_unit != nullptr && grad_alpha != nullptr),
+             "l1_ssim_loss_masked_bwd: n_alpha > 0 needs grad_alpha_unit and grad_alpha");
+  GS_REQUIRE((((uintptr_t)grad_unit | (uintptr_t)grad_img1 | (uintptr_t)grad_alpha_unit |
+               (uintptr_t)grad_alpha) & 15) == 0,
+             "l1_ssim_loss_masked_bwd: buffers must be 16-byte aligned");
+  for (int pass = 0; pass < 2; ++pass) {
+    const int64_t m = pass ? n_alpha : n;
+    if (m == 0) continue;
+    const int64_t blocks = std::min<int64_t>((m / 4 + 255) / 256 + 1, 4096);
+    hipLaunchKernelGGL(ssim::fused_scale_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, m, pass ? grad_alpha_unit : grad_unit, g_loss,
+                       pass ? grad_alpha : grad_img1);
+  }
+  GS_CHECK_LAUNCH("l1_ssim_loss_masked_bwd");
   return 0;
 }

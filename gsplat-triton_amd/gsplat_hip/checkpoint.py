@@ -63,6 +63,12 @@ def fingerprint(tr) -> dict:
         fp[k] = _plain(getattr(tr, k))
     if tr.bilateral_grid:
         fp["bilateral_grid_shape"] = _plain(tr.bilateral_grid_shape)
+    # only when on: the fingerprints of trainers without them, and of files
+    # written before the options existed, are unchanged
+    if tr.masks is not None:
+        fp["masks"] = True
+    if tr.random_bkgd:
+        fp["random_bkgd"] = True
     if tr.strategy is not None:
         for k, v in dataclasses.asdict(tr.strategy).items():
             fp["strategy." + k] = _plain(v)

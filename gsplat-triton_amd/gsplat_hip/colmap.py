@@ -685,16 +685,17 @@ def scene_tensors(parser: Parser, split: str = "train", device="cuda", load_dept
         targets [n, h, w, 3]               float32 in [0, 1], on `device`
         width, height                      the images' (undistorted) size
         masks [n, h, w] bool or None       fisheye validity masks (all true for
-                                           the other cameras); `Trainer` does
-                                           not use them yet
+                                           the other cameras): what
+                                           `Trainer(masks=...)` takes
         depth_points                       with `load_depths`: one (points
                                            [M, 2], depths [M]) per image
         points [N, 3], rgbs [N, 3]         the SfM points, colours in [0, 1]
         scene_scale
 
-    so that `Trainer(t.pop("points"), t.pop("rgbs"), **t)` trains on the scene
-    once "masks" is taken out.  `Trainer` has one width and height: images
-    that do not all end at one size raise ValueError."""
+    so that `Trainer(t.pop("points"), t.pop("rgbs"), **t)` trains on the scene,
+    the render zeroed outside each image's mask before the loss.  `Trainer` has
+    one width and height: images that do not all end at one size raise
+    ValueError."""
     import torch
     from PIL import Image as PILImage
     from .undistort import undistort_images

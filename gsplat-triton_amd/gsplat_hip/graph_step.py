@@ -192,13 +192,20 @@ BLOCK = (
     ("c2w", 1536, "float32", 16),  # 2DGS: the camera-to-world matrix (its normals)
     ("slot", SLOT - 8, "int64", 1),
 )
+# Fields of the same block that only an option's launch reads, in the free
+# range after mcmc_scale (their own table: BLOCK's field set is what every
+# captured step reads): random_bkgd's colour of the step (Trainer.bkgd_at),
+# which the loss launch reads from the block's device copy
+BLOCK_OPTIONS = (
+    ("bkgd", 276, "float32", 3),
+)
 _ITEM = {"float32": 4, "int64": 8}
 
 
 def _check_block():
     """No two fields overlap, each is aligned and inside the block."""
     end = 0
-    for name, off, dt, n in sorted(BLOCK, key=lambda f: f[1]):
+    for name, off, dt, n in sorted(BLOCK + BLOCK_OPTIONS, key=lambda f: f[1]):
         assert off >= end and off % _ITEM[dt] == 0, f"step block: field {name} at {off}"
         end = off + n * _ITEM[dt]
     assert end <= SLOT, end
@@ -212,6 +219,12 @@ def block_views(buf, lib):
     (lib = torch) or a numpy array (lib = numpy)."""
     return {name: buf[off:off + n * _ITEM[dt]].view(getattr(lib, dt))
             for name, off, dt, n in BLOCK}
+
+
+def option_views(buf, lib):
+    """block_views of the options' fields (BLOCK_OPTIONS)."""
+    return {name: buf[off:off + n * _ITEM[dt]].view(getattr(lib, dt))
+            for name, off, dt, n in BLOCK_OPTIONS}
 
 
 class _Mapped:
@@ -264,6 +277,7 @@ class GraphStep:
         # device input of the graph: one block per step (BLOCK), and its fields
         self.blk = torch.zeros(SLOT, dtype=torch.uint8, device=dev)
         self.field = block_views(self.blk, torch)
+        self.opt_field = option_views(self.blk, torch)
         # the largest launch plan (the sharded optimizer's: a shard launch and a
         # remainder launch per group) and the SH-Adam's three fit the field
         assert 4 * len(tr.params) + 3 <= self.field["adam"].numel(), len(tr.params)
@@ -288,6 +302,8 @@ class GraphStep:
         self.ring_in = _Mapped(self.RING * SLOT)
         self._host = [block_views(self.ring_in.np[k * SLOT:(k + 1) * SLOT], np)
                       for k in range(self.RING)]  # the ring slots' fields
+        self._host_opt = [option_views(self.ring_in.np[k * SLOT:(k + 1) * SLOT], np)
+                          for k in range(self.RING)]
         self.ring_out = _Mapped(self.RING * 4 * 8)
         self._out = self.ring_out.np.view(np.int64).reshape(self.RING, 4)
         self._slot_ev = [None] * self.RING
@@ -327,7 +343,8 @@ class GraphStep:
             void=self.status, hyper=f["adam"],
             side_hyper={so.name: f[so.name] for so in tr.side_opts},
             loss_ring=(self.loss_ring, self.seq) if self.ring_now else None,
-            vote=self.vote, capturing=self.dp)
+            vote=self.vote, capturing=self.dp,
+            bkgd=self.opt_field["bkgd"].view(1, 3) if tr.random_bkgd else None)
         if self.dp:  # its collectives in order on this stream (ShardedAdam.capturing)
             tr.opt.capturing = True
         try:
@@ -490,6 +507,8 @@ class GraphStep:
         h["viewmats"][:16 * self.W] = self._vm_host[world_ci].reshape(-1)
         h["Ks"][:9 * self.W] = self._K_host[world_ci].reshape(-1)
         h["cam"][0] = ci
+        if tr.random_bkgd:
+            self._host_opt[slot]["bkgd"][:] = tr.bkgd_at(it)
         if tr.mcmc:
             h["mcmc_step"][0] = it
             h["mcmc_scale"][0] = 0.0 if tr.strategy.is_refine_step(it) else tr.mcmc_scaler(it)

@@ -135,6 +135,48 @@ class _L1SSIMLossFused(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+class _L1SSIMLossMasked(torch.autograd.Function):
+    """_L1SSIMLossFused on the masked render over a background colour,
+    x = (masks ? img : 0) + backgrounds * (1 - alphas), composed in the loss
+    kernel's window load (csrc/ssim.hip fused_masked_kernel): no composed image
+    and no select / composite backward through HBM.  Gradients for img
+    (zero under the mask) and alphas; arguments checked by l1_ssim_loss."""
+
+    @staticmethod
+    def forward(ctx, img, gt, lam, gt_index, out_ring, masks, alphas, backgrounds):
+        img = img.contiguous().float()
+        gt = gt.contiguous().float()
+        B, H, W, C = img.shape
+        ws = torch.empty(max(int(_lib.query("gsplat_hip_l1_ssim_loss_fused_workspace_bytes",
+                                            B, H, W, C)), 4),
+                         dtype=torch.uint8, device=img.device)
+        out = torch.empty(3, device=img.device)
+        unit = torch.empty_like(img)
+        a_unit = None if backgrounds is None else torch.empty_like(alphas)
+        ring, seq = (None, None) if out_ring is None else out_ring
+        if ring is not None:
+            assert ring.dtype == torch.float32 and ring.is_cuda and seq.dtype == torch.int64
+        _lib.call("gsplat_hip_l1_ssim_loss_masked_fwd", B, H, W, C, _ptr(img), _ptr(gt),
+                  _ptr(gt_index), _ptr(masks), _ptr(alphas if backgrounds is not None else None),
+                  _ptr(backgrounds), ctypes.c_float(lam), _ptr(out), _ptr(unit), _ptr(a_unit),
+                  _ptr(ws), _ptr(ring), 0 if ring is None else ring.numel(), _ptr(seq), _stream())
+        ctx.save_for_backward(unit, a_unit)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        unit, a_unit = ctx.saved_tensors
+        if g_loss is ONE_GRAD:  # the trainer's constant 1.0 seed: the unit gradients as they are
+            return unit, None, None, None, None, None, a_unit, None
+        g_loss = g_loss.float().contiguous()
+        grad = torch.empty_like(unit)
+        g_alpha = None if a_unit is None else torch.empty_like(a_unit)
+        _lib.call("gsplat_hip_l1_ssim_loss_masked_bwd", unit.numel(), _ptr(unit),
+                  0 if a_unit is None else a_unit.numel(), _ptr(a_unit), _ptr(g_loss), _ptr(grad),
+                  _ptr(g_alpha), _stream())
+        return grad, None, None, None, None, None, g_alpha, None
+
+
 # A constant scalar 1.0 the trainer seeds loss.backward() with (never written):
 # seen as the incoming gradient, the fused loss's backward returns its stored
 # unit gradient without the scaling launch.
@@ -144,8 +186,59 @@ ONE_GRAD = None
 SSIM_FUSED = os.environ.get("GSPLAT_HIP_SSIM_FUSED", "1") != "0"
 
 
+def _masked_args(img, gt, gt_index, masks, alphas, backgrounds, _channels):
+    """l1_ssim_loss's checks of masks / alphas / backgrounds (ValueError naming
+    the argument); returns masks as uint8 (a view of a bool tensor)."""
+    if _channels is not None:
+        raise ValueError("l1_ssim_loss: _channels does not go with masks / backgrounds")
+    if img.dim() != 4:
+        raise ValueError(f"l1_ssim_loss: masks / backgrounds need img [B,H,W,C], got "
+                         f"{tuple(img.shape)}")
+    B, H, W, C = img.shape
+    if masks is not None:
+        if masks.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"l1_ssim_loss: masks must be bool or uint8, got {masks.dtype}")
+        want = (gt.shape[0] if gt_index is not None else B, H, W)
+        if tuple(masks.shape) != want:
+            raise ValueError(f"l1_ssim_loss: masks must be {list(want)}, got "
+                             f"{list(masks.shape)}")
+        if masks.device != img.device:
+            raise ValueError(f"l1_ssim_loss: masks on {masks.device}, img on {img.device}")
+        masks = masks.contiguous()
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+    if backgrounds is not None:
+        if alphas is None:
+            raise ValueError("l1_ssim_loss: backgrounds needs alphas")
+        if tuple(backgrounds.shape) != (B, C) or backgrounds.dtype != torch.float32 \
+                or backgrounds.device != img.device:
+            raise ValueError(f"l1_ssim_loss: backgrounds must be float32 [{B}, {C}] on "
+                             f"{img.device}, got {backgrounds.dtype} {list(backgrounds.shape)} "
+                             f"on {backgrounds.device}")
+    if alphas is not None:
+        if tuple(alphas.shape) != (B, H, W, 1) or alphas.dtype != torch.float32 \
+                or not alphas.is_contiguous() or alphas.device != img.device:
+            raise ValueError(f"l1_ssim_loss: alphas must be contiguous float32 [{B}, {H}, {W}, 1] "
+                             f"on {img.device}, got {alphas.dtype} {list(alphas.shape)} on "
+                             f"{alphas.device}")
+    return masks
+
+
+def compose_masked(img, masks=None, alphas=None, backgrounds=None):
+    """(masks ? img : 0) + backgrounds * (1 - alphas) in torch ops: img
+    [B,H,W,C], masks [B,H,W] bool / uint8 (non-zero = valid), alphas
+    [B,H,W,1], backgrounds [B,C] -- simple_trainer.py:505-506, 629-631.  What
+    the fused loss composes in its kernel; the paths without it call this."""
+    x = img
+    if masks is not None:
+        x = torch.where(masks.bool()[..., None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+    if backgrounds is not None:
+        x = x + backgrounds[:, None, None, :] * (1.0 - alphas)
+    return x
+
+
 def l1_ssim_loss(img, gt, ssim_lambda=0.2, fused=None, gt_index=None, _out_ring=None,
-                 _channels=None):
+                 _channels=None, masks=None, alphas=None, backgrounds=None):
     """(1 - ssim_lambda) * mean L1 + ssim_lambda * (1 - mean SSIM_valid).
     With a gradient to compute (and C in {1, 3}) the one-pass fused kernel
     runs, unless `fused=False` (or GSPLAT_HIP_SSIM_FUSED=0).  `gt_index`
@@ -155,7 +248,29 @@ def l1_ssim_loss(img, gt, ssim_lambda=0.2, fused=None, gt_index=None, _out_ring=
     gt_index): (ring, seq) device tensors; the loss value is also written to
     ring[(seq - 1) % len(ring)] by the reduction launch (graph_step.py).
     `_channels` (internal): the loss is over img[..., :_channels] (an RGB+D
-    render read in place by the fused kernel; its gradient is img-shaped)."""
+    render read in place by the fused kernel; its gradient is img-shaped).
+    `masks` (bool / uint8 [B,H,W], True = valid; with gt_index a stack [n,H,W]
+    indexed like gt), `alphas` ([B,H,W,1] float32 contiguous, as
+    rasterization() returns them) and `backgrounds` ([B,C] float32 on the
+    device, needs alphas): the loss is taken on
+    (masks ? img : 0) + backgrounds * (1 - alphas), the reference trainer's
+    masks and random_bkgd.  With a gradient to compute and C in {1, 3} that is
+    one kernel with gradients for img (exactly zero under the mask, whatever
+    img holds there) and alphas; otherwise torch ops (compose_masked) in
+    front of the paths above.  backgrounds and masks get no gradient."""
+    if masks is not None or backgrounds is not None:
+        masks = _masked_args(img, gt, gt_index, masks, alphas, backgrounds, _channels)
+        needs = torch.is_grad_enabled() and (
+            img.requires_grad or (backgrounds is not None and alphas.requires_grad))
+        if fused is None:
+            fused = SSIM_FUSED and needs
+        if fused and img.shape[-1] in (1, 3):
+            return _L1SSIMLossMasked.apply(img, gt, float(ssim_lambda), gt_index, _out_ring,
+                                           masks, alphas, backgrounds)
+        if gt_index is not None:
+            raise ValueError("l1_ssim_loss: gt_index needs the fused kernel (grad, C in {1, 3})")
+        return l1_ssim_loss(compose_masked(img, masks, alphas, backgrounds), gt, ssim_lambda,
+                            fused=fused)
     if _channels is not None and _channels != img.shape[-1]:
         if fused is None:
             fused = SSIM_FUSED and torch.is_grad_enabled() and img.requires_grad

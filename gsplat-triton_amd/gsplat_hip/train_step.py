@@ -234,6 +234,7 @@ class StepInputs:
     hyper: Optional[torch.Tensor] = None  # the Gaussians' Adam factors (Trainer._layout order)
     side_hyper: dict = dataclasses.field(default_factory=dict)  # SideOptimizer.name -> factors
     loss_ring: Optional[tuple] = None  # l1_ssim_loss's _out_ring
+    bkgd: Optional[torch.Tensor] = None  # random_bkgd: the step's colour, device float32 [1,3]
     vote: bool = False  # several ranks: agree on the void flag beside the loss kernels
     capturing: bool = False  # sharded optimizer: collectives in order, no deferred gather
 
@@ -273,6 +274,12 @@ _REFUSALS = {
              ("model='2dgs'",) + _SPARSE + ("antialiased", "opacity_reg", "scale_reg") + _MANY
              + ("fused=False", "GSPLAT_HIP_GEOM_FUSE=0", "GSPLAT_HIP_GEOM_IN_PROJ=0")),
     "bilateral_grid": ("the one-GPU dense 3DGS trainer only", ("model='2dgs'",) + _SPARSE + _MANY),
+    # (the mask belongs before the grid's slice, and the depth step has a loss
+    # node of its own: both are follow-ups)
+    "masks": ("the one-GPU dense 3DGS trainer only",
+              ("model='2dgs'",) + _SPARSE + _MANY + ("bilateral_grid", "depth_loss")),
+    "random_bkgd": ("the one-GPU dense 3DGS trainer only",
+                    ("model='2dgs'",) + _SPARSE + _MANY + ("bilateral_grid", "depth_loss")),
     "normal_loss / dist_loss": ("the one-GPU dense 2DGS trainer only",
                                 ("packed", "sparse_grad") + _MANY),
     "compression": ("one-GPU trainers only", _MANY),
@@ -309,6 +316,8 @@ class Trainer:
     model = "3dgs"
     bilateral_grid = pose_opt = depth_loss = app_opt = False
     pose_noise = 0.0
+    masks = None
+    random_bkgd = False
     normal_loss = dist_loss = False
     gshard = packed = sparse_grad = visible_adam = mcmc = False
     sh_adam_in_bwd = geom_fuse = geom_in_proj = geom_applied = False
@@ -342,7 +351,8 @@ class Trainer:
                  pose_opt: bool = False, pose_opt_lr: float = 1e-5, pose_opt_reg: float = 1e-6,
                  pose_noise: float = 0.0, depth_loss: bool = False, depth_lambda: float = 1e-2,
                  depth_points=None, app_opt: bool = False, app_embed_dim: int = 16,
-                 app_opt_lr: float = 1e-3, app_opt_reg: float = 1e-6):
+                 app_opt_lr: float = 1e-3, app_opt_reg: float = 1e-6,
+                 masks: Optional[torch.Tensor] = None, random_bkgd: bool = False):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
         # the options of the one-GPU dense trainer, each refused with what it
@@ -356,7 +366,25 @@ class Trainer:
             "gaussian_shard": gaussian_shard, "sharded_optimizer": sharded_optimizer,
             "world_size": world_size != 1, "fused=False": not fused,
             "GSPLAT_HIP_GEOM_FUSE=0": env("GSPLAT_HIP_GEOM_FUSE", "1") == "0",
-            "GSPLAT_HIP_GEOM_IN_PROJ=0": env("GSPLAT_HIP_GEOM_IN_PROJ", "1") == "0"}
+            "GSPLAT_HIP_GEOM_IN_PROJ=0": env("GSPLAT_HIP_GEOM_IN_PROJ", "1") == "0",
+            "bilateral_grid": bool(bilateral_grid), "depth_loss": bool(depth_loss)}
+        # simple_trainer.py:505-506 (masks: the render zeroed outside each
+        # image's mask before the loss -- an undistorted fisheye image's
+        # validity mask, colmap.scene_tensors(parser)["masks"], or the user's
+        # own) and random_bkgd (:629-631: a fresh random colour under the
+        # render every step); both composed inside the loss kernel
+        # (losses.l1_ssim_loss masks / alphas / backgrounds)
+        self.random_bkgd = bool(random_bkgd)
+        if masks is not None:
+            _refuse("masks", asked)
+            if masks.dtype != torch.bool or tuple(masks.shape) != (len(viewmats), height, width):
+                raise ValueError(f"masks: bool [{len(viewmats)}, {height}, {width}] (True = "
+                                 f"valid), got {masks.dtype} {list(masks.shape)}")
+            # one uint8 table on the device beside the targets: the loss picks
+            # the step's image by the device index it picks the target by
+            self.masks = masks.to(device).contiguous().view(torch.uint8)
+        if self.random_bkgd:
+            _refuse("random_bkgd", asked)
         # simple_trainer.py app_opt / app_embed_dim / app_opt_lr / app_opt_reg
         # (:243-254, 389-410): the colours from the appearance MLP over
         # `features` [N,32], a per-image embedding and the view direction's SH
@@ -1171,9 +1199,31 @@ class Trainer:
             stats=self.strategy is None or (not self.mcmc
                                             and it < self.strategy.refine_stop_iter),
             viewmats=vms, Ks=Ks, cam=self._cam_index[ci:ci + 1], targets=self.targets[ci:ci + 1],
-            c2w=self.camtoworld(ci) if self.model == "2dgs" else None, it=it))
+            c2w=self.camtoworld(ci) if self.model == "2dgs" else None, it=it,
+            bkgd=(torch.tensor([self.bkgd_at(it)], dtype=torch.float32, device=self.device)
+                  if self.random_bkgd else None)))
         self.last_meta = meta
         return loss
+
+    def bkgd_at(self, it: int):
+        """random_bkgd's colour of step `it`: three float32 in [0, 1), a pure
+        function of (the trainer's seed, it) -- a counter-based host generator
+        (splitmix64 of the counter) keyed by the seed's noise key, which a
+        checkpoint already carries; no stream state, nothing drawn from
+        self.rng.  Eager, replayed and resumed steps therefore see the same
+        colours.  (The reference draws torch.rand(1, 3) from the global
+        generator: the same distribution, another sequence.)"""
+        m64 = (1 << 64) - 1
+        out = []
+        for ch in range(3):
+            z = (int(self._noise_seed) ^ ((3 * int(it) + ch + 1) * 0xD1B54A32D192ED03)) & m64
+            for _ in range(2):  # splitmix64's finaliser, twice
+                z = (z + 0x9E3779B97F4A7C15) & m64
+                z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m64
+                z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m64
+                z ^= z >> 31
+            out.append(float(np.float32((z >> 40) * (1.0 / (1 << 24)))))  # 24 bits: exact, < 1
+        return tuple(out)
 
     def _layout(self):
         """(groups of the Gaussians' Adam launches in launch order, offset of
@@ -1228,12 +1278,25 @@ class Trainer:
             photo, term, tv = self.depth_losses(meta["_rgbd"], alphas, s.targets, s.cam,
                                                 gt_index=s.gt_index)
             loss = photo + term
+        elif self.fused and (self.masks is not None or self.random_bkgd):
+            # the render masked and put over the step's colour inside the loss kernel
+            m = self.masks
+            if m is not None and s.gt_index is None:
+                m = m.index_select(0, s.cam)  # (eager: the image's own [1,H,W])
+            loss = l1_ssim_loss(colors, s.targets, self.ssim_lambda, gt_index=s.gt_index,
+                                _out_ring=s.loss_ring, masks=m, alphas=alphas,
+                                backgrounds=s.bkgd)
         elif self.fused:  # (2DGS: the RGB+D render's colour channels in place)
             two = self.model == "2dgs"
             loss = l1_ssim_loss(meta["_rgbd"] if two else colors, s.targets, self.ssim_lambda,
                                 gt_index=s.gt_index, _out_ring=s.loss_ring,
                                 _channels=3 if two else None)
         else:
+            if self.masks is not None or self.random_bkgd:  # the same, in torch ops
+                from .losses import compose_masked
+                colors = compose_masked(
+                    colors, None if self.masks is None else self.masks.index_select(0, s.cam),
+                    alphas, s.bkgd)
             l1 = F.l1_loss(colors, s.targets)
             ssim_loss = 1.0 - ssim(colors.permute(0, 3, 1, 2), s.targets.permute(0, 3, 1, 2),
                                    self.window)
@@ -1287,6 +1350,8 @@ class Trainer:
                     continue
                 p.grad = torch.sparse_coo_tensor(indices=ids[None], values=g[ids], size=p.size(),
                                                  is_coalesced=meta["n_cameras"] == 1)
+            self.opt.step()
+        elif isinstance(self.opt, torch.optim.Optimizer):  # fused=False: torch's Adam
             self.opt.step()
         else:
             skip = self._sh_skip(fusion)
@@ -1423,17 +1488,27 @@ class Trainer:
 
     # ---------------------------------------------------------------- eval
     @torch.no_grad()
-    def evaluate(self, cameras=None, viewmats=None, Ks=None, images=None):
+    def evaluate(self, cameras=None, viewmats=None, Ks=None, images=None, masks=None):
         """simple_trainer.py:854-932's eval metrics: render each camera,
         clamp to [0, 1], PSNR (data range 1) and SSIM (11x11 Gaussian, the
         fused "valid" SSIM of the loss) against the target, averaged.  Either
         indices into the trainer's camera pool / targets, or explicit
         viewmats [M,4,4], Ks [M,3,3] and images [M,H,W,3].  LPIPS is not
-        computed (its network weights are a download)."""
+        computed (its network weights are a download).  A trainer with masks
+        zeroes each pool camera's render outside its mask before the metrics
+        (simple_trainer.py:871-884 passes the masks to the render); `masks`
+        [M,H,W] bool does so for the explicit form.  No background is added."""
         self.sync()
         if viewmats is None:
             idx = list(range(len(self.viewmats))) if cameras is None else list(cameras)
             viewmats, Ks, images = self.viewmats[idx], self.Ks[idx], self.targets[idx]
+            if masks is None and self.masks is not None:
+                masks = self.masks[idx]
+        if masks is not None:
+            if tuple(masks.shape) != (len(viewmats), self.height, self.width):
+                raise ValueError(f"evaluate: masks [{len(viewmats)}, {self.height}, "
+                                 f"{self.width}], got {list(masks.shape)}")
+            masks = masks.to(self.device).bool()
         psnrs, ssims = [], []
         saved = self.viewmats, self.Ks
         try:
@@ -1442,6 +1517,9 @@ class Trainer:
             for i in range(len(viewmats)):
                 # Gaussian-sharded: every rank renders camera i (a collective)
                 colors, _, _ = self.render(i, world_ci=[i] * self.world_size)
+                if masks is not None:
+                    colors = torch.where(masks[i:i + 1, ..., None], colors,
+                                         torch.zeros((), device=colors.device))
                 colors = torch.clamp(colors, 0.0, 1.0)
                 gt = images[i:i + 1].to(self.device)
                 mse = torch.mean((colors - gt) ** 2)

@@ -66,7 +66,9 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_app_workspace_bytes (appearance optimisation);
  *     gsplat_hip_kmeans_l1_assign, gsplat_hip_kmeans_update and
  *     gsplat_hip_kmeans_update_workspace_bytes (splat compression);
- *     gsplat_hip_ply_count / _pack / _unpack / _workspace_bytes (PLY rows). */
+ *     gsplat_hip_ply_count / _pack / _unpack / _workspace_bytes (PLY rows);
+ *     gsplat_hip_l1_ssim_loss_masked_fwd / _bwd (the 3DGS trainer's per-image
+ *     masks and random background, composed in the loss kernel). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -499,6 +501,35 @@ int gsplat_hip_l1_ssim_loss_fused_fwd_ring(int B, int H, int W, int C, int x_str
                                            float lam, float *out, float *grad_unit,
                                            void *workspace, float *loss_ring, int64_t ring_len,
                                            const int64_t *seq_device, void *stream);
+/* The fused loss on a masked render over a background colour (the 3DGS
+ * trainer's masks / random_bkgd, simple_trainer.py:505-506, 629-631), composed
+ * in the loss kernel's window load:
+ *   x = (mask ? img1 : 0) + bkgd[b][c] * (1 - alpha),  loss as fused_fwd on x.
+ * masked_fwd: mask (may be NULL: all valid) uint8 [B,H,W], non-zero = valid,
+ *   or with img2_index a stack [n,H,W] whose image img2_index[0] is taken, as
+ *   for img2; alpha float [B,H,W] and bkgd float [B,C] in device memory (both
+ *   read only when bkgd is not NULL, which then needs alpha and
+ *   grad_alpha_unit).  img1 and grad_unit have C floats per pixel, C 1 or 3,
+ *   H * W * C < 2^31.  grad_unit = mask ? dout[0]/dx : 0 (a non-finite img1
+ *   under the mask reaches neither the loss nor a gradient); grad_alpha_unit
+ *   [B,H,W] = -sum_c bkgd[b][c] dout[0]/dx_c, at masked pixels too, untouched
+ *   when bkgd is NULL.  Results are bit-identical from run to run.  workspace
+ *   as fused_fwd; loss_ring / ring_len / seq_device as fused_fwd_ring, a NULL
+ *   ring: no ring write.
+ * masked_bwd: grad_img1 = g_loss[0] * grad_unit (n floats) and, with
+ *   n_alpha > 0, grad_alpha = g_loss[0] * grad_alpha_unit (n_alpha floats);
+ *   16-B aligned buffers.
+ * (Added to ABI 38 without a new number: new entries only.) */
+int gsplat_hip_l1_ssim_loss_masked_fwd(int B, int H, int W, int C, const float *img1,
+                                       const float *img2, const int64_t *img2_index,
+                                       const uint8_t *mask, const float *alpha,
+                                       const float *bkgd, float lam, float *out,
+                                       float *grad_unit, float *grad_alpha_unit,
+                                       void *workspace, float *loss_ring, int64_t ring_len,
+                                       const int64_t *seq_device, void *stream);
+int gsplat_hip_l1_ssim_loss_masked_bwd(int64_t n, const float *grad_unit, int64_t n_alpha,
+                                       const float *grad_alpha_unit, const float *g_loss,
+                                       float *grad_img1, float *grad_alpha, void *stream);
 
 /* The captured training step's per-step input without copy engines (ABI 22;
  * gsplat_hip/graph_step.py, not a reference function):
