@@ -1,5 +1,5 @@
 // The geometry groups' Adam step inside a projection backward: the 3DGS one
-// (projection.hip, ABI 31) and the 2DGS one (surfel.hip, ABI 33).
+// (projection.hip, ABI 31) and the 2DGS one (surfel_projection.hip, ABI 33).
 #pragma once
 
 #include "common.h"

@@ -13,7 +13,7 @@
 namespace gs {
 
 // the packed-count scan (projection.hip), also used by projection_covar.hip
-// and the 2DGS packed projection (surfel.hip)
+// and the 2DGS packed projection (surfel_projection.hip)
 void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st);
 
 struct Cam {

@@ -610,7 +610,7 @@ extern "C" int gsplat_hip_projection_bwd_adam_pose(
 }
 
 namespace gs {
-// the packed-count scan, shared with the 2DGS packed projection (surfel.hip)
+// the packed-count scan, shared with the 2DGS packed projection (surfel_projection.hip)
 void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st) {
   hipLaunchKernelGGL(packed_scan_kernel, dim3(1), dim3(1024), 0, st, nb, cnt, total);
 }

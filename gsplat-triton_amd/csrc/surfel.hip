@@ -1,18 +1,12 @@
-// 2DGS (surfel) hot path for gfx950: ray-splat projection and the surfel
-// rasterizer, forward and backward.
+// 2DGS (surfel) rasterizer for gfx950, forward and backward.  The ray-splat
+// projection that feeds it is surfel_projection.hip.
 //
 // Replaces the reference CUDA kernels (hieu1999210/gsplat-triton)
-//   projection_2dgs_fused_fwd_kernel   gsplat/cuda/csrc/Projection2DGSFused.cu:17-238
-//   projection_2dgs_fused_bwd_kernel   gsplat/cuda/csrc/Projection2DGSFused.cu:319-457
-//     (+ compute_ray_transforms_aabb_vjp, gsplat/cuda/csrc/Projection2DGS.cuh:10-87)
 //   rasterize_to_pixels_2dgs_fwd_kernel gsplat/cuda/csrc/RasterizeToPixels2DGSFwd.cu:18-452
 //   rasterize_to_pixels_2dgs_bwd_kernel gsplat/cuda/csrc/RasterizeToPixels2DGSBwd.cu:16-700
 // with the same per-pixel algebra, on a CDNA4 mapping:
 //
-//  * projection: one lane per (camera, surfel), grid (ceil(N/256), C) so the
-//    camera is a wave-uniform scalar load; the backward stores its gradients
-//    (atomics only when several cameras share a surfel).
-//  * rasterizer: a workgroup per tile, each wave64 owns 64 consecutive pixels
+//  * forward: a workgroup per tile, each wave64 owns 64 consecutive pixels
 //    of the tile (a 16x4 strip of a 16x16 tile) and walks the tile's isects on
 //    its own: the lanes gather 64 records into a per-wave LDS queue, then every
 //    lane composites its pixel against the queue with LDS broadcast reads.  No
@@ -25,8 +19,6 @@
 //    unpack_kernel scatters the rows into the autograd tensors and forms the
 //    densification gradient.
 #include "common.h"
-#include "geom_adam.h"
-#include "proj_math.h"  // launch_packed_scan; Cam here is surfel::Cam
 #include "wave_ops.h"
 #include "surfel_cull.h"
 #include "../../include/gsplat_hip.h"
@@ -39,302 +31,6 @@ constexpr float kTMin = 1e-4f;
 constexpr float kFilterInvSquare = 2.f;  // FILTER_INV_SQUARE_2DGS, Rasterization.h:11
 constexpr float kLog2e = 1.4426950408889634f;
 
-// ------------------------------------------------------------- projection
-struct ProjFwdArgs {
-  int C, N, W, H;
-  float near_plane, far_plane, radius_clip;
-  const float *means, *quats, *scales, *viewmats, *Ks;
-  int32_t *radii;
-  float *means2d, *depths, *ray_transforms, *normals;
-  // packed mode (projection_2dgs_packed_fwd, Projection2DGSPacked.cu:17-205):
-  // per-block counts of kept (camera, surfel) pairs, then their exclusive
-  // prefix, in (c, n) order
-  int64_t *block_cnt;
-  const int64_t *block_off;
-  int64_t *camera_ids, *gaussian_ids;
-};
-
-struct Cam {
-  M3 R;
-  float t[3], fx, fy, cx, cy;
-};
-
-GS_INLINE Cam load_cam(const float *__restrict__ viewmats, const float *__restrict__ Ks, int c) {
-  Cam k;
-  const float *V = viewmats + 16 * c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) k.R.m[i][j] = V[4 * i + j];
-    k.t[i] = V[4 * i + 3];
-  }
-  const float *K = Ks + 9 * c;  // the reference reads K[0], K[2], K[4], K[5] only
-  k.fx = K[0];
-  k.cx = K[2];
-  k.fy = K[4];
-  k.cy = K[5];
-  return k;
-}
-
-// Camera-space surfel: mean, the two scaled tangent axes and the normal axis
-// (columns of R_cw * R(q) * diag(s0, s1, 1), Projection2DGSFused.cu:164-167).
-struct Frame {
-  float mc[3], t0[3], t1[3], nz[3];
-  M3 Rq;
-};
-
-GS_INLINE Frame surfel_frame(const Cam &k, const float *m, float4 q, float s0, float s1) {
-  Frame f;
-  f.Rq = quat_to_rotmat(q.x, q.y, q.z, q.w);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    f.mc[i] = k.R.m[i][0] * m[0] + k.R.m[i][1] * m[1] + k.R.m[i][2] * m[2] + k.t[i];
-    float a = 0.f, b = 0.f, c = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      a += k.R.m[i][j] * f.Rq.m[j][0];
-      b += k.R.m[i][j] * f.Rq.m[j][1];
-      c += k.R.m[i][j] * f.Rq.m[j][2];
-    }
-    f.t0[i] = a * s0;
-    f.t1[i] = b * s1;
-    f.nz[i] = c;
-  }
-  return f;
-}
-
-// MODE 0: dense [C, N] outputs.  MODE 1: count the kept pairs per block.
-// MODE 2: write the kept pairs packed at block_off[block] + rank in block.
-template <int MODE>
-__global__ void __launch_bounds__(256) proj_fwd_kernel(ProjFwdArgs a) {
-  const int c = blockIdx.y;
-  const int n_raw = blockIdx.x * blockDim.x + threadIdx.x;
-  const Cam k = load_cam(a.viewmats, a.Ks, c);
-  if (MODE == 0 && n_raw >= a.N) return;
-  const bool in = n_raw < a.N;
-  const int n = in ? n_raw : a.N - 1;  // packed modes: every lane reaches the block scan
-  const size_t idx = (size_t)c * a.N + n;
-  const float4 q = *reinterpret_cast<const float4 *>(a.quats + 4 * (size_t)n);
-  const float *sp = a.scales + 3 * (size_t)n;
-  const Frame f = surfel_frame(k, a.means + 3 * (size_t)n, q, sp[0], sp[1]);
-  if (MODE == 0) a.depths[idx] = f.mc[2];
-
-  // rows of K * [t0 | t1 | mc] (the ray transform, M0/M1/M2 of the reference)
-  float M[9];
-  M[0] = k.fx * f.t0[0] + k.cx * f.t0[2];
-  M[1] = k.fx * f.t1[0] + k.cx * f.t1[2];
-  M[2] = k.fx * f.mc[0] + k.cx * f.mc[2];
-  M[3] = k.fy * f.t0[1] + k.cy * f.t0[2];
-  M[4] = k.fy * f.t1[1] + k.cy * f.t1[2];
-  M[5] = k.fy * f.mc[1] + k.cy * f.mc[2];
-  M[6] = f.t0[2];
-  M[7] = f.t1[2];
-  M[8] = f.mc[2];
-
-  bool keep = in && !(f.mc[2] < a.near_plane || f.mc[2] > a.far_plane);
-  // AABB from the (1, 1, -1) corner (Projection2DGSFused.cu:200-219)
-  const float dist = M[6] * M[6] + M[7] * M[7] - M[8] * M[8];
-  keep &= dist != 0.f;
-  const float fi = 1.f / dist;
-  const float mx = (fi * M[0]) * M[6] + (fi * M[1]) * M[7] + (-fi * M[2]) * M[8];
-  const float my = (fi * M[3]) * M[6] + (fi * M[4]) * M[7] + (-fi * M[5]) * M[8];
-  const float ex = mx * mx - ((fi * M[0]) * M[0] + (fi * M[1]) * M[1] + (-fi * M[2]) * M[2]);
-  const float ey = my * my - ((fi * M[3]) * M[3] + (fi * M[4]) * M[4] + (-fi * M[5]) * M[5]);
-  const float radius = ceilf(3.f * sqrtf(fmaxf(1e-4f, fmaxf(ex, ey))));
-  keep &= radius > a.radius_clip;
-  keep &= !(mx + radius <= 0.f || mx - radius >= (float)a.W || my + radius <= 0.f ||
-            my - radius >= (float)a.H);
-
-  const float sgn = -(f.nz[0] * f.mc[0] + f.nz[1] * f.mc[1] + f.nz[2] * f.mc[2]) > 0.f ? 1.f : -1.f;
-  if (MODE == 0) {
-    a.radii[idx] = keep ? (int32_t)radius : 0;
-    *reinterpret_cast<float2 *>(a.means2d + 2 * idx) = keep ? make_float2(mx, my) : make_float2(0.f, 0.f);
-    float *rt = a.ray_transforms + 9 * idx;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rt[i] = keep ? M[i] : 0.f;
-    float *nr = a.normals + 3 * idx;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) nr[i] = keep ? sgn * f.nz[i] : 0.f;
-    return;
-  }
-  // packed: rank of this pair among the block's kept pairs (wave ballots)
-  __shared__ int wave_cnt[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint64_t m = __ballot(keep);
-  if (lane == 0) wave_cnt[wid] = __popcll(m);
-  __syncthreads();
-  const int64_t blk = (int64_t)c * gridDim.x + blockIdx.x;
-  if (MODE == 1) {
-    if (threadIdx.x == 0) a.block_cnt[blk] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    return;
-  }
-  if (!keep) return;
-  int before = 0;
-  for (int w = 0; w < wid; ++w) before += wave_cnt[w];
-  const int64_t o = a.block_off[blk] + before +
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-  a.camera_ids[o] = c;
-  a.gaussian_ids[o] = n;
-  a.radii[o] = (int32_t)radius;
-  *reinterpret_cast<float2 *>(a.means2d + 2 * o) = make_float2(mx, my);
-  a.depths[o] = f.mc[2];
-  float *rt = a.ray_transforms + 9 * o;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) rt[i] = M[i];
-  float *nr = a.normals + 3 * o;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) nr[i] = sgn * f.nz[i];
-}
-
-struct ProjBwdArgs {
-  int C, N;
-  const float *means, *quats, *scales, *viewmats, *Ks;
-  const int32_t *radii;
-  const float *ray_transforms, *v_means2d, *v_depths, *v_normals, *v_ray_transforms;
-  float *v_means, *v_quats, *v_scales;
-  int store_mode;  // C == 1: plain stores of every row; else atomics of valid rows
-  // packed inputs (projection_2dgs_packed_bwd, Projection2DGSPacked.cu:274-420):
-  // entry e is the pair (camera_ids[e], gaussian_ids[e]); sparse: one
-  // gradient row per entry [nnz, .]
-  const int64_t *camera_ids, *gaussian_ids;
-  int64_t nnz;
-  int sparse;
-  GeomAdam ga;  // proj_bwd_kernel: the geometry Adam instead of the stores
-};
-
-// a.ga.p[0] set (ABI 33, gsplat_hip_projection_2dgs_bwd_adam; C == 1,
-// dense): the geometry groups' Adam step on the lane's rows instead of
-// storing v_means / v_quats / v_scales (geom_adam.h).  A runtime branch of
-// the one kernel, so that the fused update consumes exactly the gradient
-// values the plain backward stores (two instantiations contracted the
-// algebra differently: 1 ulp in the log-scales).
-__global__ void __launch_bounds__(256) proj_bwd_kernel(ProjBwdArgs a) {
-  int c, n;
-  size_t idx;
-  bool valid;
-  const bool packed = a.camera_ids != nullptr;
-  if (packed) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.nnz) return;
-    c = (int)a.camera_ids[e];
-    n = (int)a.gaussian_ids[e];
-    idx = (size_t)e;
-    valid = true;
-  } else {
-    c = blockIdx.y;
-    n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= a.N) return;
-    idx = (size_t)c * a.N + n;
-    valid = a.radii[idx] > 0;
-  }
-  GeomRows gr;
-  const bool fuse = a.ga.p[0] != nullptr;
-  const bool fuse_on = fuse && !(a.ga.skip && *a.ga.skip);
-  if (fuse_on) geom_rows_load(a.ga, (size_t)n, a.scales, gr);  // in flight from here
-  const Cam k = load_cam(a.viewmats, a.Ks, c);
-  float vm[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-  if (valid) {
-    const float4 q = *reinterpret_cast<const float4 *>(a.quats + 4 * (size_t)n);
-    const float *sp = a.scales + 3 * (size_t)n;
-    const float s0 = sp[0], s1 = sp[1];
-    const Frame f = surfel_frame(k, a.means + 3 * (size_t)n, q, s0, s1);
-    const float *rt = a.ray_transforms + 9 * idx;
-    float V[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) V[i] = a.v_ray_transforms[9 * idx + i];
-    if (a.v_depths) V[8] += a.v_depths[idx];
-    // means2d through the AABB formula, as the reference differentiates it
-    // (Projection2DGS.cuh:25-65)
-    const float gx = a.v_means2d[2 * idx], gy = a.v_means2d[2 * idx + 1];
-    if (gx != 0.f || gy != 0.f) {
-      float r[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) r[i] = rt[i];
-      const float fi = 1.f / (r[6] * r[6] + r[7] * r[7] - r[8] * r[8]);
-      const float f2 = 2.f * fi * fi;
-      V[0] += gx * (fi * r[6]);
-      V[1] += gx * (fi * r[7]);
-      V[2] += gx * (-fi * r[8]);
-      V[3] += gy * (fi * r[6]);
-      V[4] += gy * (fi * r[7]);
-      V[5] += gy * (-fi * r[8]);
-      const float e6 = fi - f2 * r[6] * r[6], e7 = fi - f2 * r[7] * r[7], e8 = fi + f2 * r[8] * r[8];
-      V[6] += gx * (r[0] * e6) + gy * (r[3] * e6);
-      V[7] += gx * (r[1] * e7) + gy * (r[4] * e7);
-      V[8] += gx * (-r[2] * e8) + gy * (-r[5] * e8);
-    }
-    // d/d[t0 | t1 | mc] = K^T V (camera space), then R^T to world
-    float dW[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      dW[0][j] = k.fx * V[j];
-      dW[1][j] = k.fy * V[3 + j];
-      dW[2][j] = k.cx * V[j] + k.cy * V[3 + j] + V[6 + j];
-    }
-    float vRS[3][3];  // vRS[i][j]: world-space gradient of column j
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        vRS[i][j] = k.R.m[0][i] * dW[0][j] + k.R.m[1][i] * dW[1][j] + k.R.m[2][i] * dW[2][j];
-    // v_normals may be null (ABI 33: a render whose normals carry no
-    // gradient): zeros through the same arithmetic
-    float gn[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gn[i] = a.v_normals ? a.v_normals[3 * idx + i] : 0.f;
-    const float sgn =
-        -(f.nz[0] * f.mc[0] + f.nz[1] * f.mc[1] + f.nz[2] * f.mc[2]) > 0.f ? 1.f : -1.f;
-    float vtn[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      vtn[i] = sgn * (k.R.m[0][i] * gn[0] + k.R.m[1][i] * gn[1] + k.R.m[2][i] * gn[2]);
-    M3 dR;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      dR.m[i][0] = vRS[i][0] * s0;
-      dR.m[i][1] = vRS[i][1] * s1;
-      dR.m[i][2] = vtn[i];
-    }
-    quat_to_rotmat_vjp(q.x, q.y, q.z, q.w, dR, vq);
-    vs[0] = vRS[0][0] * f.Rq.m[0][0] + vRS[1][0] * f.Rq.m[1][0] + vRS[2][0] * f.Rq.m[2][0];
-    vs[1] = vRS[0][1] * f.Rq.m[0][1] + vRS[1][1] * f.Rq.m[1][1] + vRS[2][1] * f.Rq.m[2][1];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vm[i] = vRS[i][2];
-  }
-  // the gradients are formed once, here, for every epilogue below, each
-  // rounded on its own: the fused Adam epilogue (FUSE) then consumes exactly
-  // the values the plain kernel stores (without the barrier the compiler may
-  // contract the algebra differently in the two instantiations)
-  asm volatile("" : "+v"(vm[0]), "+v"(vm[1]), "+v"(vm[2]), "+v"(vq[0]), "+v"(vq[1]),
-               "+v"(vq[2]), "+v"(vq[3]), "+v"(vs[0]), "+v"(vs[1]), "+v"(vs[2]));
-  if (fuse) {
-    if (fuse_on) geom_rows_update(a.ga, (size_t)n, gr, vm, vs, vq);
-    return;
-  }
-  if (packed && a.sparse) {  // COO values, one row per packed entry
-    float *o = a.v_means + 3 * idx;
-    o[0] = vm[0]; o[1] = vm[1]; o[2] = vm[2];
-    *reinterpret_cast<float4 *>(a.v_quats + 4 * idx) = make_float4(vq[0], vq[1], vq[2], vq[3]);
-    o = a.v_scales + 3 * idx;
-    o[0] = vs[0]; o[1] = vs[1]; o[2] = 0.f;
-  } else if (a.store_mode) {
-    float *o = a.v_means + 3 * (size_t)n;
-    o[0] = vm[0]; o[1] = vm[1]; o[2] = vm[2];
-    *reinterpret_cast<float4 *>(a.v_quats + 4 * (size_t)n) = make_float4(vq[0], vq[1], vq[2], vq[3]);
-    o = a.v_scales + 3 * (size_t)n;
-    o[0] = vs[0]; o[1] = vs[1]; o[2] = 0.f;
-  } else if (valid) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) atomic_add_f32(a.v_means + 3 * (size_t)n + j, vm[j]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) atomic_add_f32(a.v_quats + 4 * (size_t)n + j, vq[j]);
-    atomic_add_f32(a.v_scales + 3 * (size_t)n, vs[0]);
-    atomic_add_f32(a.v_scales + 3 * (size_t)n + 1, vs[1]);
-  }
-}
-
-// ------------------------------------------------------------- rasterizer
 // Record of one isect in a wave's LDS queue (floats):
 //   [0] x [1] y [2] opacity [3] isect index (int bits)
 //   [4..13) ray transform rows u, v, w   [13] surfel id (int bits)
@@ -387,19 +83,64 @@ GS_INLINE int order_tile(const RasterArgs &a) {
   return b < a.n_tiles ? a.order[b] : -1;
 }
 
-// Pixel of lane `lane` in wave `w`: the 64w + lane-th pixel of the tile in
-// row-major order (a 16x4 strip for 16x16 tiles).
-struct Pix {
-  int c, tile, px, py;
-  bool inside;
-  int64_t pid;  // flat pixel index in [C*H*W] (clamped)
+// A tile's camera, position in the tile grid and isect range (load_range():
+// called by Pix and Pix2 where their kernels had the loads).
+struct TileAt {
+  int tile, c, tx, ty;
   int64_t start, end;
-  GS_INLINE Pix(const RasterArgs &a, int tile_, int w, int lane) {
+  GS_INLINE TileAt(const RasterArgs &a, int tile_) {
     tile = tile_;
     const int ntile = a.tw * a.th;
     c = tile / ntile;
     const int rem = tile - c * ntile;
-    const int ty = rem / a.tw, tx = rem - ty * a.tw;
+    ty = rem / a.tw;
+    tx = rem - ty * a.tw;
+  }
+  GS_INLINE void load_range(const RasterArgs &a) {
+    start = a.offsets[tile];
+    end = (tile == a.n_tiles - 1) ? (a.n_dev ? a.n_dev[0] : a.n_isects)
+                                  : (int64_t)a.offsets[tile + 1];
+  }
+};
+
+// The two pixels of lane `lane` in wave `w` of a 16x16 tile (two waves): the
+// wave owns the 16x8 band of rows 8w..8w+7, the lane the pixels
+// (lane & 15, 8w + (lane >> 4)) and 4 rows below.  Pixel k's row, inside flag
+// and flat index are methods, formed where a kernel asks for them: the step's
+// kernels are held to the instructions they had with the decode written out.
+struct Pix2 : TileAt {
+  int lane, row;         // row: the band's first row
+  float x0, x1, y0, y1;  // pixel-centre rectangle of the band
+  GS_INLINE Pix2(const RasterArgs &a, int tile_, int w_, int lane_)
+      : TileAt(a, tile_), lane(lane_) {
+    load_range(a);
+    x0 = tx * 16 + 0.5f;
+    x1 = x0 + 15.f;
+    row = ty * 16 + 8 * w_;
+    y0 = row + 0.5f;
+    y1 = y0 + 7.f;
+  }
+  GS_INLINE int px() const { return tx * 16 + (lane & 15); }
+  GS_INLINE int py(int k) const { return row + 4 * k + (lane >> 4); }
+  GS_INLINE bool inside(const RasterArgs &a, int py) const { return px() < a.W && py < a.H; }
+  // flat index in [C*H*W] of the pixel in row py, inside the image
+  GS_INLINE int64_t pid(const RasterArgs &a, int py) const {
+    return ((int64_t)c * a.H + py) * a.W + tx * 16 + (lane & 15);
+  }
+  // the same, or for a lane outside the image (in false) the camera's first
+  // pixel: the backward loads there
+  GS_INLINE int64_t pid_or_first(const RasterArgs &a, int py, bool in) const {
+    return (int64_t)c * a.H * a.W + (in ? (int64_t)py * a.W + px() : 0);
+  }
+};
+
+// Pixel of lane `lane` in wave `w`: the 64w + lane-th pixel of the tile in
+// row-major order (a 16x4 strip for 16x16 tiles).
+struct Pix : TileAt {
+  int px, py;
+  bool inside;
+  int64_t pid;  // flat pixel index in [C*H*W] (clamped)
+  GS_INLINE Pix(const RasterArgs &a, int tile_, int w, int lane) : TileAt(a, tile_) {
     const int p = 64 * w + lane;
     const int ly = p / a.ts, lx = p - ly * a.ts;
     px = tx * a.ts + lx;
@@ -407,9 +148,7 @@ struct Pix {
     inside = (p < a.ts * a.ts) && px < a.W && py < a.H;
     const int64_t off = (int64_t)c * a.H * a.W;
     pid = off + (inside ? (int64_t)py * a.W + px : 0);
-    start = a.offsets[tile];
-    end = (tile == a.n_tiles - 1) ? (a.n_dev ? a.n_dev[0] : a.n_isects)
-                                  : (int64_t)a.offsets[tile + 1];
+    load_range(a);
     // pixel-centre rectangle of the wave's rows (whole tile width)
     const int r0 = (64 * w) / a.ts, r1 = min(a.ts - 1, (64 * w + 63) / a.ts);
     x0 = tx * a.ts + 0.5f;
@@ -546,16 +285,6 @@ GS_INLINE void read_f4(const float *slot, float (&v)[NF]) {
   }
 }
 
-template <int D>
-GS_INLINE void read_rec(const float *slot, float (&v)[Rec<D>::NF]) {
-  const float4 *s4 = reinterpret_cast<const float4 *>(slot);
-#pragma unroll
-  for (int q = 0; q < Rec<D>::N4; ++q) {
-    const float4 t = s4[q];
-    v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-  }
-}
-
 // Ray-splat evaluation of one record at pixel centre (px, py)
 // (RasterizeToPixels2DGSFwd.cu:333-361).
 struct Hit {
@@ -584,6 +313,89 @@ GS_INLINE Hit eval_hit(const float *m, float x, float y, float op, float px, flo
   h.alpha = fminf(kAlphaMax, op * h.vis);
   h.ok = (h.rc[2] != 0.f) && !(sigma < 0.f) && !(h.alpha < kAlphaMin);
   return h;
+}
+
+// One record into one pixel: the forward's compositing step.  The pixel centre
+// is (fx, fy); the caller passes the fx part of the linear ray-splat form
+// (FRec), r*b = fx * A + Cc, and dx2 = (x - fx)^2, which the two pixels of a
+// lane share.  LEAN: only the colours, T and the last id.  Called by
+// fwd2_kernel and fwd2s_kernel; fwd_kernel has the statements written out
+// (called from it: more VGPRs; profiles/surfel_split/README.md).
+template <int D, bool LEAN>
+GS_INLINE void blend_pixel(bool &done, float &T, float (&col)[D], float (&nrm)[3], float &distort,
+                           float &acc_vd, float &median, int32_t &cur, int32_t &med, float fy,
+                           float rxb, float ryb, float rzb, float bx, float by, float bz,
+                           float dx2, float y, float op, float smax, const float *c, float n0,
+                           float n1, float n2, int32_t idx) {
+  if (done) return;
+  const float rx = fy * bx + rxb;
+  const float ry = fy * by + ryb;
+  const float rz = fy * bz + rzb;
+  const float iz = __builtin_amdgcn_rcpf(rz);
+  const float g3 = (rx * rx + ry * ry) * (iz * iz);
+  const float dy = y - fy;
+  const float g2 = kLog2e * (dx2 + dy * dy);
+  const float m = fminf(g3, g2);  // sigma * log2(e)
+  if (rz != 0.f && m <= smax) {
+    const float alpha = fminf(kAlphaMax, op * __builtin_amdgcn_exp2f(-m));
+    const float nT = T * (1.f - alpha);
+    if (nT <= kTMin) {
+      done = true;
+    } else {
+      const float vis = alpha * T;
+#pragma unroll
+      for (int d = 0; d < D; ++d) col[d] += c[d] * vis;
+      if (!LEAN) {
+        nrm[0] += n0 * vis;
+        nrm[1] += n1 * vis;
+        nrm[2] += n2 * vis;
+        const float depth = c[D - 1];
+        distort += 2.f * (vis * depth * (1.f - T) - vis * acc_vd);
+        acc_vd += vis * depth;
+        if (T > 0.5f) {
+          median = depth;
+          med = idx;
+        }
+      }
+      cur = idx;
+      T = nT;
+    }
+  }
+}
+
+// A pixel's outputs, for every forward kernel (the state one variable at a
+// time, here as in blend_pixel: as a struct it changed fwd2s_kernel's
+// registers).  A masked tile's pixel: the reference writes the background
+// only; the rest is defined here as empty.  LEAN: colours, alpha, last id.
+template <int D, bool LEAN>
+GS_INLINE void write_pixel(const RasterArgs &a, int64_t pid, bool masked, const float *bg, float T,
+                           const float (&col)[D], const float (&nrm)[3], float distort,
+                           float median, int32_t cur, int32_t med) {
+  if (masked) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? bg[d] : 0.f;
+    a.render_alphas[pid] = 0.f;
+    a.last_ids[pid] = 0;
+    if (!LEAN) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = 0.f;
+      a.render_distort[pid] = 0.f;
+      a.render_median[pid] = 0.f;
+      a.median_ids[pid] = 0;
+    }
+    return;
+  }
+  a.render_alphas[pid] = 1.f - T;
+#pragma unroll
+  for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? col[d] + T * bg[d] : col[d];
+  a.last_ids[pid] = cur;
+  if (!LEAN) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = nrm[i];
+    a.render_distort[pid] = distort;
+    a.render_median[pid] = median;
+    a.median_ids[pid] = med;
+  }
 }
 
 // One workgroup per tile, ceil(ts^2 / 64) waves, a 64-record queue per wave.
@@ -624,7 +436,7 @@ __global__ void __launch_bounds__(1024) fwd_kernel(RasterArgs a) {
     for (int t = 0; t < n; ++t) {
       float r[R::NF];
       read_f4<R::NF>(q + t * R::NF, r);
-      if (!done) {
+      if (!done) {  // blend_pixel<D, false>, written out (see its comment)
         const float rx = fx * r[R::A] + fy * r[R::B] + r[R::CC];
         const float ry = fx * r[R::A + 1] + fy * r[R::B + 1] + r[R::CC + 1];
         const float rz = fx * r[R::A + 2] + fy * r[R::B + 2] + r[R::CC + 2];
@@ -661,38 +473,15 @@ __global__ void __launch_bounds__(1024) fwd_kernel(RasterArgs a) {
     }
     wave_sync_lds();
   }
-  if (!p.inside) return;
-  const int64_t pid = p.pid;
-  if (masked) {  // reference writes the background only; the rest is defined here as empty
-#pragma unroll
-    for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? bg[d] : 0.f;
-    a.render_alphas[pid] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = 0.f;
-    a.render_distort[pid] = 0.f;
-    a.render_median[pid] = 0.f;
-    a.last_ids[pid] = 0;
-    a.median_ids[pid] = 0;
-    return;
-  }
-  a.render_alphas[pid] = 1.f - T;
-#pragma unroll
-  for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? col[d] + T * bg[d] : col[d];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = nrm[i];
-  a.render_distort[pid] = distort;
-  a.render_median[pid] = median;
-  a.last_ids[pid] = cur;
-  a.median_ids[pid] = med;
+  if (p.inside)
+    write_pixel<D, false>(a, p.pid, masked, bg, T, col, nrm, distort, median, cur, med);
 }
 
-// Forward with two pixels per lane (tile_size 16): wave w of the 2 owns the
-// 16x8 band of rows 8w..8w+7, lane l the pixels (l & 15, 8w + (l >> 4)) and
-// 4 rows below.  Two independent transmittance chains per lane give the
-// scheduler independent work between dependent steps, and the gather,
-// culling test and LDS reads of a record are shared by both pixels.  Same
-// per-pixel arithmetic as fwd_kernel.
-template <int D, bool LEAN = false>  // LEAN: fwd2s_kernel's colours-only form (unused here)
+// Forward with two pixels per lane (tile_size 16; Pix2).  Two independent
+// transmittance chains per lane give the scheduler independent work between
+// dependent steps, and the gather, culling test and LDS reads of a record are
+// shared by both pixels.  Same per-pixel arithmetic as fwd_kernel.
+template <int D>
 __global__ void __launch_bounds__(128) fwd2_kernel(RasterArgs a) {
   using R = FRec<D>;
   extern __shared__ float4 lds4[];
@@ -700,26 +489,18 @@ __global__ void __launch_bounds__(128) fwd2_kernel(RasterArgs a) {
   float *q = reinterpret_cast<float *>(lds4) + (size_t)w * 64 * R::NF;
   const int tile = order_tile(a);
   if (tile < 0) return;
-  const int ntile = a.tw * a.th;
-  const int c = tile / ntile;
-  const int rem = tile - c * ntile;
-  const int ty = rem / a.tw, tx = rem - ty * a.tw;
-  const int64_t start = a.offsets[tile];
-  const int64_t end = (tile == a.n_tiles - 1) ? (a.n_dev ? a.n_dev[0] : a.n_isects)
-                                              : (int64_t)a.offsets[tile + 1];
-  const float rx0 = tx * 16 + 0.5f, rx1 = rx0 + 15.f;
-  const float ry0 = ty * 16 + 8 * w + 0.5f, ry1 = ry0 + 7.f;
-  const float *bg = a.backgrounds ? a.backgrounds + (int64_t)c * D : nullptr;
+  const Pix2 p(a, tile, w, lane);
+  const float *bg = a.backgrounds ? a.backgrounds + (int64_t)p.c * D : nullptr;
   const bool masked = a.masks && !a.masks[tile];
-  const float fx = (float)(tx * 16 + (lane & 15)) + 0.5f;
+  const float fx = (float)p.px() + 0.5f;
   float fy[2], T[2], col[2][D], nrm[2][3], distort[2], acc_vd[2], median[2];
   int32_t cur[2], med[2];
   bool done[2], inside[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const int py = ty * 16 + 8 * w + 4 * k + (lane >> 4);
+    const int py = p.py(k);
     fy[k] = (float)py + 0.5f;
-    inside[k] = (tx * 16 + (lane & 15)) < a.W && py < a.H;
+    inside[k] = p.inside(a, py);
     T[k] = 1.f;
 #pragma unroll
     for (int d = 0; d < D; ++d) col[k][d] = 0.f;
@@ -730,19 +511,19 @@ __global__ void __launch_bounds__(128) fwd2_kernel(RasterArgs a) {
     done[k] = !inside[k] || masked;
   }
 
-  int64_t b = start;
-  const bool run = !masked && b < end;
+  int64_t b = p.start;
+  const bool run = !masked && b < p.end;
   Gathered<D> nxt;
-  if (run) gather<D>(a, b + lane, b + lane < end, nxt);
-  for (; run && b < end; b += 64) {
+  if (run) gather<D>(a, b + lane, b + lane < p.end, nxt);
+  for (; run && b < p.end; b += 64) {
     if (__ballot(!(done[0] & done[1])) == 0) break;
-    const bool keep = (b + lane < end) &&
-                      surfel_keep(nxt.m, nxt.xy.x, nxt.xy.y, nxt.op, rx0, rx1, ry0, ry1);
+    const bool keep = (b + lane < p.end) &&
+                      surfel_keep(nxt.m, nxt.xy.x, nxt.xy.y, nxt.op, p.x0, p.x1, p.y0, p.y1);
     const uint64_t km = __ballot(keep);
     const int n = __popcll(km);
     if (keep) stage_fwd<D>(q + ballot_slot(km) * R::NF, nxt, (int32_t)(b + lane));
     wave_sync_lds();
-    if (b + 64 < end) gather<D>(a, b + 64 + lane, b + 64 + lane < end, nxt);
+    if (b + 64 < p.end) gather<D>(a, b + 64 + lane, b + 64 + lane < p.end, nxt);
     for (int t = 0; t < n; ++t) {
       float r[R::NF];
       read_f4<R::NF>(q + t * R::NF, r);
@@ -750,95 +531,28 @@ __global__ void __launch_bounds__(128) fwd2_kernel(RasterArgs a) {
                   rzb = fx * r[R::A + 2] + r[R::CC + 2];
       const float dx = r[R::X] - fx, dx2 = dx * dx;
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        if (done[k]) continue;
-        const float rx = fy[k] * r[R::B] + rxb;
-        const float ry = fy[k] * r[R::B + 1] + ryb;
-        const float rz = fy[k] * r[R::B + 2] + rzb;
-        const float iz = __builtin_amdgcn_rcpf(rz);
-        const float g3 = (rx * rx + ry * ry) * (iz * iz);
-        const float dy = r[R::Y] - fy[k];
-        const float g2 = kLog2e * (dx2 + dy * dy);
-        const float m = fminf(g3, g2);  // sigma * log2(e)
-        if (rz != 0.f && m <= r[R::SMAX]) {
-          const float alpha = fminf(kAlphaMax, r[R::OP] * __builtin_amdgcn_exp2f(-m));
-          const float nT = T[k] * (1.f - alpha);
-          if (nT <= kTMin) {
-            done[k] = true;
-          } else {
-            const float vis = alpha * T[k];
-#pragma unroll
-            for (int d = 0; d < D; ++d) col[k][d] += r[R::COL + d] * vis;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) nrm[k][i] += r[R::NRM + i] * vis;
-            const float depth = r[R::COL + D - 1];
-            distort[k] += 2.f * (vis * depth * (1.f - T[k]) - vis * acc_vd[k]);
-            acc_vd[k] += vis * depth;
-            const int32_t idx = __float_as_int(r[R::IDX]);
-            if (T[k] > 0.5f) {
-              median[k] = depth;
-              med[k] = idx;
-            }
-            cur[k] = idx;
-            T[k] = nT;
-          }
-        }
-      }
+      for (int k = 0; k < 2; ++k)
+        blend_pixel<D, false>(done[k], T[k], col[k], nrm[k], distort[k], acc_vd[k], median[k],
+                              cur[k], med[k], fy[k], rxb, ryb, rzb, r[R::B], r[R::B + 1],
+                              r[R::B + 2], dx2, r[R::Y], r[R::OP], r[R::SMAX], r + R::COL,
+                              r[R::NRM], r[R::NRM + 1], r[R::NRM + 2], __float_as_int(r[R::IDX]));
       if ((t & 7) == 7 && __ballot(!(done[0] & done[1])) == 0) break;
     }
     wave_sync_lds();
   }
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (!inside[k]) continue;
-    const int64_t pid = ((int64_t)c * a.H + (ty * 16 + 8 * w + 4 * k + (lane >> 4))) * a.W +
-                        tx * 16 + (lane & 15);
-    if (masked) {  // as fwd_kernel
-#pragma unroll
-      for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? bg[d] : 0.f;
-      a.render_alphas[pid] = 0.f;
-      a.last_ids[pid] = 0;
-      if (!LEAN) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = 0.f;
-        a.render_distort[pid] = 0.f;
-        a.render_median[pid] = 0.f;
-        a.median_ids[pid] = 0;
-      }
-      continue;
-    }
-    a.render_alphas[pid] = 1.f - T[k];
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-      a.render_colors[pid * D + d] = bg ? col[k][d] + T[k] * bg[d] : col[k][d];
-    a.last_ids[pid] = cur[k];
-    if (!LEAN) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = nrm[k][i];
-      a.render_distort[pid] = distort[k];
-      a.render_median[pid] = median[k];
-      a.median_ids[pid] = med[k];
-    }
-  }
+  for (int k = 0; k < 2; ++k)
+    if (inside[k])  // pid(): valid for a pixel inside the image only
+      write_pixel<D, false>(a, p.pid(a, p.py(k)), masked, bg, T[k], col[k], nrm[k], distort[k],
+                            median[k], cur[k], med[k]);
 }
 
-// ---- Scalar-operand records (GSPLAT_HIP_SURFEL_SREC=1; D <= 4, 16x16
-// tiles).  fwd2_kernel spends, per (record, wave), six ds_read_b128 on the
-// staged record (every lane reads the same 96 B: 48 of the CU's 128 B/clk LDS
-// cycles) besides the staging writes.  Here pack_srec_kernel writes one 128-B
-// record per surfel with everything the culling test and the compositing
-// read, precomputed; the lanes cull their candidates from vector loads of the
-// first 80 B, and the kept records are composited in ascending isect order
-// from scalar loads (constant address space, wave-uniform address from
-// v_readlane of the candidate's id): the fields reach the VALU as SGPR
-// operands, with no LDS traffic at all.  Same per-pixel arithmetic and order
-// as fwd2_kernel (bit-identical outputs).
-// Dispatch order (GSPLAT_HIP_SURFEL_ORDER=1): the tiles bucketed by
-// floor(log2(isects)), heaviest bucket first, so the longest tiles start in
-// the first wave of workgroups instead of finishing last (order inside a
-// bucket: arrival at an LDS counter).  One workgroup; any tile count: the
-// tiles are taken in blocks of 16384 (16 per thread), and with more than one
-// block each pass reloads its block's keys.
+// Dispatch order (the caller asks for it by passing tile_order): the tiles
+// bucketed by floor(log2(isects)), heaviest bucket first, so the longest
+// tiles start in the first wave of workgroups instead of finishing last
+// (order inside a bucket: arrival at an LDS counter).  One workgroup; any tile
+// count: the tiles are taken in blocks of 16384 (16 per thread), and with more
+// than one block each pass reloads its block's keys.
 __global__ void __launch_bounds__(1024)
 tile_order_kernel(int n_tiles, const int32_t *__restrict__ offsets, int64_t n_isects,
                   const int64_t *__restrict__ n_dev, int32_t *__restrict__ order) {
@@ -908,6 +622,17 @@ tile_order_kernel(int n_tiles, const int32_t *__restrict__ offsets, int64_t n_is
   }
 }
 
+// ---- Scalar-operand records (D <= kSRecMaxD, 16x16 tiles; the caller asks
+// for them by passing records).  fwd2_kernel spends, per (record, wave), six
+// ds_read_b128 on the staged record (every lane reads the same 96 B: 48 of the
+// CU's 128 B/clk LDS cycles) besides the staging writes.  Here
+// pack_srec_kernel writes one 128-B record per surfel with everything the
+// culling test and the compositing read, precomputed; the lanes cull their
+// candidates from vector loads of the first 80 B, and the kept records are
+// composited in ascending isect order from scalar loads (constant address
+// space, wave-uniform address from v_readlane of the candidate's id): the
+// fields reach the VALU as SGPR operands, with no LDS traffic at all.  The
+// compositing step and its order are fwd2_kernel's.
 constexpr int kSRecMaxD = 4;
 namespace srec {
 // floats of a record
@@ -1074,26 +799,18 @@ __global__ void __launch_bounds__(128) fwd2s_kernel(RasterArgs a, const float *_
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int tile = order_tile(a);
   if (tile < 0) return;
-  const int ntile = a.tw * a.th;
-  const int c = tile / ntile;
-  const int rem = tile - c * ntile;
-  const int ty = rem / a.tw, tx = rem - ty * a.tw;
-  const int64_t start = a.offsets[tile];
-  const int64_t end = (tile == a.n_tiles - 1) ? (a.n_dev ? a.n_dev[0] : a.n_isects)
-                                              : (int64_t)a.offsets[tile + 1];
-  const float rx0 = tx * 16 + 0.5f, rx1 = rx0 + 15.f;
-  const float ry0 = ty * 16 + 8 * w + 0.5f, ry1 = ry0 + 7.f;
-  const float *bg = a.backgrounds ? a.backgrounds + (int64_t)c * D : nullptr;
+  const Pix2 p(a, tile, w, lane);
+  const float *bg = a.backgrounds ? a.backgrounds + (int64_t)p.c * D : nullptr;
   const bool masked = a.masks && !a.masks[tile];
-  const float fx = (float)(tx * 16 + (lane & 15)) + 0.5f;
+  const float fx = (float)p.px() + 0.5f;
   float fy[2], T[2], col[2][D], nrm[2][3], distort[2], acc_vd[2], median[2];
   int32_t cur[2], med[2];
   bool done[2], inside[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const int py = ty * 16 + 8 * w + 4 * k + (lane >> 4);
+    const int py = p.py(k);
     fy[k] = (float)py + 0.5f;
-    inside[k] = (tx * 16 + (lane & 15)) < a.W && py < a.H;
+    inside[k] = p.inside(a, py);
     T[k] = 1.f;
 #pragma unroll
     for (int d = 0; d < D; ++d) col[k][d] = 0.f;
@@ -1103,64 +820,32 @@ __global__ void __launch_bounds__(128) fwd2s_kernel(RasterArgs a, const float *_
     cur[k] = med[k] = 0;
     done[k] = !inside[k] || masked;
   }
-  // one record into both pixels of the lane (fwd2_kernel's arithmetic)
+  // one record into both pixels of the lane
   auto blend = [&](const SBlend<D> &r, int32_t idx) {
     const float rxb = fx * r.ax + r.cx, ryb = fx * r.ay + r.cy, rzb = fx * r.az + r.cz;
     const float dx = r.x - fx, dx2 = dx * dx;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (done[k]) continue;
-      const float rx = fy[k] * r.bx + rxb;
-      const float ry = fy[k] * r.by + ryb;
-      const float rz = fy[k] * r.bz + rzb;
-      const float iz = __builtin_amdgcn_rcpf(rz);
-      const float g3 = (rx * rx + ry * ry) * (iz * iz);
-      const float dy = r.y - fy[k];
-      const float g2 = kLog2e * (dx2 + dy * dy);
-      const float m = fminf(g3, g2);
-      if (rz != 0.f && m <= r.smax) {
-        const float alpha = fminf(kAlphaMax, r.op * __builtin_amdgcn_exp2f(-m));
-        const float nT = T[k] * (1.f - alpha);
-        if (nT <= kTMin) {
-          done[k] = true;
-        } else {
-          const float vis = alpha * T[k];
-#pragma unroll
-          for (int d = 0; d < D; ++d) col[k][d] += r.col[d] * vis;
-          if (!LEAN) {
-            nrm[k][0] += r.n0 * vis;
-            nrm[k][1] += r.n1 * vis;
-            nrm[k][2] += r.n2 * vis;
-            const float depth = r.col[D - 1];
-            distort[k] += 2.f * (vis * depth * (1.f - T[k]) - vis * acc_vd[k]);
-            acc_vd[k] += vis * depth;
-            if (T[k] > 0.5f) {
-              median[k] = depth;
-              med[k] = idx;
-            }
-          }
-          cur[k] = idx;
-          T[k] = nT;
-        }
-      }
-    }
+    for (int k = 0; k < 2; ++k)
+      blend_pixel<D, LEAN>(done[k], T[k], col[k], nrm[k], distort[k], acc_vd[k], median[k], cur[k],
+                           med[k], fy[k], rxb, ryb, rzb, r.bx, r.by, r.bz, dx2, r.y, r.op, r.smax,
+                           r.col, r.n0, r.n1, r.n2, idx);
   };
 
-  int64_t b = start;
-  const bool run = !masked && b < end;
+  int64_t b = p.start;
+  const bool run = !masked && b < p.end;
   int32_t gn = 0;
   SCull kn;
   if (run) {
-    gn = b + lane < end ? a.flatten_ids[b + lane] : 0;
+    gn = b + lane < p.end ? a.flatten_ids[b + lane] : 0;
     srec_load_cull(rec, gn, kn);
   }
-  for (; run && b < end; b += 64) {
+  for (; run && b < p.end; b += 64) {
     if (__ballot(!(done[0] & done[1])) == 0) break;
-    const bool keep = (b + lane < end) && srec_keep(kn, rx0, rx1, ry0, ry1);
+    const bool keep = (b + lane < p.end) && srec_keep(kn, p.x0, p.x1, p.y0, p.y1);
     uint64_t km = __ballot(keep);
     const int32_t gc = gn;
-    if (b + 64 < end) {  // the next batch's candidates, in flight while this one composites
-      gn = b + 64 + lane < end ? a.flatten_ids[b + 64 + lane] : 0;
+    if (b + 64 < p.end) {  // the next batch's candidates, in flight while this one composites
+      gn = b + 64 + lane < p.end ? a.flatten_ids[b + 64 + lane] : 0;
       srec_load_cull(rec, gn, kn);
     }
     // kept records in ascending isect order, two per round: both records'
@@ -1184,37 +869,10 @@ __global__ void __launch_bounds__(128) fwd2s_kernel(RasterArgs a, const float *_
     }
   }
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (!inside[k]) continue;
-    const int64_t pid = ((int64_t)c * a.H + (ty * 16 + 8 * w + 4 * k + (lane >> 4))) * a.W +
-                        tx * 16 + (lane & 15);
-    if (masked) {  // as fwd_kernel
-#pragma unroll
-      for (int d = 0; d < D; ++d) a.render_colors[pid * D + d] = bg ? bg[d] : 0.f;
-      a.render_alphas[pid] = 0.f;
-      a.last_ids[pid] = 0;
-      if (!LEAN) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = 0.f;
-        a.render_distort[pid] = 0.f;
-        a.render_median[pid] = 0.f;
-        a.median_ids[pid] = 0;
-      }
-      continue;
-    }
-    a.render_alphas[pid] = 1.f - T[k];
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-      a.render_colors[pid * D + d] = bg ? col[k][d] + T[k] * bg[d] : col[k][d];
-    a.last_ids[pid] = cur[k];
-    if (!LEAN) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a.render_normals[pid * 3 + i] = nrm[k][i];
-      a.render_distort[pid] = distort[k];
-      a.render_median[pid] = median[k];
-      a.median_ids[pid] = med[k];
-    }
-  }
+  for (int k = 0; k < 2; ++k)
+    if (inside[k])  // pid(): valid for a pixel inside the image only
+      write_pixel<D, LEAN>(a, p.pid(a, p.py(k)), masked, bg, T[k], col[k], nrm[k], distort[k],
+                            median[k], cur[k], med[k]);
 }
 
 // Gradient fields of a packed row: colour[D], normal[3], ray transform[9],
@@ -1292,7 +950,7 @@ __global__ void __launch_bounds__(256) bwd_kernel(RasterArgs a) {
     wave_sync_lds();
     for (int t = n - 1; t >= 0; --t) {
       float r[R::NF];
-      read_rec<D>(q + t * R::NF, r);
+      read_f4<R::NF>(q + t * R::NF, r);
       const int32_t idx = __float_as_int(r[R::IDX]);
       const float *m = r + R::M;
       Hit h = eval_hit(m, r[R::X], r[R::Y], r[R::OP], fx, fy);
@@ -1380,12 +1038,11 @@ __global__ void __launch_bounds__(256) bwd_kernel(RasterArgs a) {
   }
 }
 
-// Backward with two pixels per lane (tile_size 16): wave w of the 2 owns
-// the 16x8 band of rows 8w..8w+7, lane l the pixels (l & 15, 8w + (l >> 4))
-// and 4 rows below.  Both pixels' gradient terms of a record are summed
-// in-lane before the one reduce-scatter of the D + 15 fields, halving the
-// cross-lane work, LDS reads and atomics per pixel (as bwd2_kernel of
-// rasterize16.hip).  Same per-pixel arithmetic as bwd_kernel.
+// Backward with two pixels per lane (tile_size 16; Pix2).  Both pixels'
+// gradient terms of a record are summed in-lane before the one reduce-scatter
+// of the D + 15 fields, halving the cross-lane work, LDS reads and atomics per
+// pixel (as bwd2_kernel of rasterize16.hip).  Same per-pixel arithmetic as
+// bwd_kernel.
 template <int D>
 struct PixState {
   float T, tfvb, vc[D], buf[D], vn[3], bufn[3], vdist, accum_d, accum_w, accd_buf, accw_buf,
@@ -1412,23 +1069,16 @@ bwd2_kernel(RasterArgs a) {
   const int tile = order_tile(a);
   if (tile < 0) return;
   if (a.masks && !a.masks[tile]) return;
-  const int ntile = a.tw * a.th;
-  const int c = tile / ntile;
-  const int rem = tile - c * ntile;
-  const int ty = rem / a.tw, tx = rem - ty * a.tw;
-  const int64_t start = a.offsets[tile];
-  const int64_t tend = (tile == a.n_tiles - 1) ? (a.n_dev ? a.n_dev[0] : a.n_isects)
-                                               : (int64_t)a.offsets[tile + 1];
-  const float rx0 = tx * 16 + 0.5f, rx1 = rx0 + 15.f;
-  const float ry0 = ty * 16 + 8 * w + 0.5f, ry1 = ry0 + 7.f;
+  const Pix2 p(a, tile, w, lane);
+  const int64_t start = p.start;
   PixState<D> ps[2];
   int32_t wmax = 0;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     PixState<D> &s = ps[k];
-    const int px = tx * 16 + (lane & 15), py = ty * 16 + 8 * w + 4 * k + (lane >> 4);
-    s.inside = px < a.W && py < a.H;
-    const int64_t pid = (int64_t)c * a.H * a.W + (s.inside ? (int64_t)py * a.W + px : 0);
+    const int px = p.px(), py = p.py(k);
+    s.inside = p.inside(a, py);
+    const int64_t pid = p.pid_or_first(a, py, s.inside);  // outside lanes load too
     s.fx = (float)px + 0.5f;
     s.fy = (float)py + 0.5f;
     const float Tf = 1.f - a.render_alphas[pid];
@@ -1440,7 +1090,7 @@ bwd2_kernel(RasterArgs a) {
     for (int d = 0; d < D; ++d) {
       s.vc[d] = a.v_render_colors[pid * D + d];
       s.buf[d] = 0.f;
-      if (a.backgrounds) bg_dot += a.backgrounds[(int64_t)c * D + d] * s.vc[d];
+      if (a.backgrounds) bg_dot += a.backgrounds[(int64_t)p.c * D + d] * s.vc[d];
     }
     s.tfvb = Tf * ((a.v_render_alphas ? a.v_render_alphas[pid] : 0.f) - bg_dot);
     if (!LEAN) {
@@ -1461,7 +1111,7 @@ bwd2_kernel(RasterArgs a) {
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) wmax = max(wmax, __shfl_xor(wmax, m, 64));
-  const int64_t end = min(tend, (int64_t)wmax + 1);
+  const int64_t end = min(p.end, (int64_t)wmax + 1);
   const int lf = rs_field(lane);
   // LEAN: the two pixels' state as packed pairs (.x pixel 0, .y pixel 1)
   f2v T2 = f2v{ps[0].T, ps[1].T}, tfvb2 = f2v{ps[0].tfvb, ps[1].tfvb};
@@ -1496,7 +1146,7 @@ bwd2_kernel(RasterArgs a) {
       } else {
         gather<D>(a, j, j < b1, g);
       }
-      const bool keep = (j < b1) && surfel_keep(g.m, g.xy.x, g.xy.y, g.op, rx0, rx1, ry0, ry1);
+      const bool keep = (j < b1) && surfel_keep(g.m, g.xy.x, g.xy.y, g.op, p.x0, p.x1, p.y0, p.y1);
       const uint64_t km = __ballot(keep);
       n = __popcll(km);
       if (keep) stage<D>(q + ballot_slot(km) * R::NF, g, (int32_t)j);
@@ -1504,7 +1154,7 @@ bwd2_kernel(RasterArgs a) {
     wave_sync_lds();
     for (int t = n - 1; t >= 0; --t) {
       float r[R::NF];
-      read_rec<D>(q + t * R::NF, r);
+      read_f4<R::NF>(q + t * R::NF, r);
       const int32_t idx = __float_as_int(r[R::IDX]);
       const float *m = r + R::M;
       Hit h[2];
@@ -1806,9 +1456,6 @@ unpack_kernel(int64_t G, const int32_t *__restrict__ visible, const float *__res
 }  // namespace surfel
 }  // namespace gs
 
-namespace gs {
-int dbg_flags();  // rasterize16.hip: GSPLAT_HIP_DBG / gsplat_hip_debug_set_flags
-}
 using namespace gs;
 using namespace gs::surfel;
 
@@ -1824,14 +1471,13 @@ bool channels_supported(int D) {
   return false;
 }
 
-// 16x16 tiles: two pixels per lane in the forward and the backward (fwd2 /
-// bwd2 kernels; the one-pixel kernels, which measured 1.62 / 1.76 against
-// 1.10 / 1.63 ms at M5, serve the other tile sizes)
-bool fwd2_enabled() { return true; }
+// The channel counts of the scalar-operand records and the LEAN backward.
+#define GS_SREC_CHANNELS(X) X(1) X(2) X(3) X(4)
+static_assert(kSRecMaxD == 4, "GS_SREC_CHANNELS lists 1..kSRecMaxD");
+
 // the XCD runs of the tile order (RasterArgs::xcd_runs; GSPLAT_HIP_DBG bit 4:
 // one tile after the other, as the 3DGS rasterizer's flag)
 int xcd_runs() { return !(gs::dbg_flags() & 16); }
-bool bwd2_enabled() { return true; }
 
 int fields_stride(int D, int absgrad) {
   const int nf = D + 15 + (absgrad ? 2 : 0);
@@ -1852,190 +1498,6 @@ int check_tiles(int C, int W, int H, int ts, int tw, int th) {
 }
 
 }  // namespace
-
-extern "C" int gsplat_hip_projection_2dgs_fwd(int C, int N, const float *means, const float *quats,
-                                              const float *scales, const float *viewmats,
-                                              const float *Ks, int width, int height,
-                                              float near_plane, float far_plane,
-                                              float radius_clip, int32_t *radii, float *means2d,
-                                              float *depths, float *ray_transforms,
-                                              float *normals, void *stream) {
-  GS_REQUIRE(C >= 0 && N >= 0, "projection_2dgs_fwd: negative sizes C=%d N=%d", C, N);
-  if (C == 0 || N == 0) return 0;
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && radii && means2d && depths &&
-                 ray_transforms && normals,
-             "projection_2dgs_fwd: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0,
-             "projection_2dgs_fwd: quats must be 16-B aligned, means2d 8-B aligned");
-  ProjFwdArgs a{C, N, width, height, near_plane, far_plane, radius_clip, means, quats, scales,
-                viewmats, Ks, radii, means2d, depths, ray_transforms, normals};
-  hipLaunchKernelGGL(proj_fwd_kernel<0>, dim3((N + 255) / 256, C), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  GS_CHECK_LAUNCH("projection_2dgs_fwd");
-  return 0;
-}
-
-extern "C" int gsplat_hip_projection_2dgs_bwd(
-    int C, int N, const float *means, const float *quats, const float *scales,
-    const float *viewmats, const float *Ks, int width, int height, const int32_t *radii,
-    const float *ray_transforms, const float *v_means2d, const float *v_depths,
-    const float *v_normals, const float *v_ray_transforms, float *v_means, float *v_quats,
-    float *v_scales, float *v_viewmats, void *stream) {
-  (void)width;
-  (void)height;
-  GS_REQUIRE(C >= 0 && N >= 0, "projection_2dgs_bwd: negative sizes C=%d N=%d", C, N);
-  hipStream_t st = (hipStream_t)stream;
-  // the reference allocates v_viewmats but its kernel never writes it
-  // (Projection2DGSFused.cu:319-457): zeros
-  if (v_viewmats && C > 0) GS_HIP(gs::zero_async(v_viewmats, sizeof(float) * 16 * C, st));
-  if (N == 0) return 0;
-  const int store_mode = (C == 1);
-  if (!store_mode) {
-    GS_HIP(gs::zero_async(v_means, sizeof(float) * 3 * N, st));
-    GS_HIP(gs::zero_async(v_quats, sizeof(float) * 4 * N, st));
-    GS_HIP(gs::zero_async(v_scales, sizeof(float) * 3 * N, st));
-  }
-  if (C == 0) return 0;
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && radii && ray_transforms &&
-                 v_means2d && v_ray_transforms && v_means && v_quats && v_scales,
-             "projection_2dgs_bwd: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0,
-             "projection_2dgs_bwd: quats / v_quats must be 16-B aligned");
-  ProjBwdArgs a{C, N, means, quats, scales, viewmats, Ks, radii, ray_transforms, v_means2d,
-                v_depths, v_normals, v_ray_transforms, v_means, v_quats, v_scales, store_mode};
-  hipLaunchKernelGGL(proj_bwd_kernel, dim3((N + 255) / 256, C), dim3(256), 0, st, a);
-  GS_CHECK_LAUNCH("projection_2dgs_bwd");
-  return 0;
-}
-
-// gsplat_hip_projection_2dgs_bwd with the geometry groups' Adam step fused in
-// (ABI 33; geom_adam.h, as gsplat_hip_projection_bwd_adam for 3DGS): one
-// camera; params / exp_avgs / exp_avg_sqs are [means, log_scales, quats,
-// logits]; lrs[4] with the 1-based step, or hyper_device f32[8]; skip_device
-// may be NULL.  No gradient is stored.
-extern "C" int gsplat_hip_projection_2dgs_bwd_adam(
-    int N, const float *means, const float *quats, const float *scales, const float *viewmats,
-    const float *Ks, const int32_t *radii, const float *ray_transforms, const float *v_means2d,
-    const float *v_depths, const float *v_normals, const float *v_ray_transforms,
-    const float *v_dirs, const float *v_opac, const float *opac, float *const *params,
-    float *const *exp_avgs, float *const *exp_avg_sqs, const float *lrs, float beta1,
-    float beta2, float eps, int step, const float *hyper_device, const int32_t *skip_device,
-    void *stream) {
-  GS_REQUIRE(N >= 0, "projection_2dgs_bwd_adam: negative N=%d", N);
-  if (N == 0) return 0;
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && radii && ray_transforms &&
-                 v_means2d && v_ray_transforms,
-             "projection_2dgs_bwd_adam: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0, "projection_2dgs_bwd_adam: quats must be 16-B aligned");
-  GeomAdam ga;
-  if (int e = geom_adam_setup(ga, params, exp_avgs, exp_avg_sqs, lrs, beta1, beta2, eps, step,
-                              hyper_device, skip_device, v_dirs, v_opac, opac,
-                              "projection_2dgs_bwd_adam"))
-    return e;
-  ProjBwdArgs a{1, N, means, quats, scales, viewmats, Ks, radii, ray_transforms, v_means2d,
-                v_depths, v_normals, v_ray_transforms, nullptr, nullptr, nullptr, 1};
-  a.ga = ga;
-  hipLaunchKernelGGL(proj_bwd_kernel, dim3((N + 255) / 256, 1), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  GS_CHECK_LAUNCH("projection_2dgs_bwd_adam");
-  return 0;
-}
-
-// ------------------------------------------------------------------ packed --
-// projection_2dgs_packed_fwd (gsplat/cuda/csrc/Projection2DGSPacked.cu:17-270):
-// a counting pass, a scan of the per-block counts and a pass that recomputes
-// and writes the kept (camera, surfel) pairs in (camera, surfel) order.
-extern "C" int64_t gsplat_hip_projection_2dgs_packed_workspace_bytes(int C, int N) {
-  const int64_t nb = (int64_t)C * ((N + 255) / 256);
-  return (nb + 1) * (int64_t)sizeof(int64_t);
-}
-
-extern "C" int gsplat_hip_projection_2dgs_packed_count(
-    int C, int N, const float *means, const float *quats, const float *scales,
-    const float *viewmats, const float *Ks, int width, int height, float near_plane,
-    float far_plane, float radius_clip, void *workspace, int64_t *nnz_device, void *stream) {
-  GS_REQUIRE(C >= 0 && N >= 0, "projection_2dgs_packed_count: negative sizes C=%d N=%d", C, N);
-  hipStream_t st = (hipStream_t)stream;
-  if (C == 0 || N == 0) {
-    GS_HIP(gs::zero_async(nnz_device, sizeof(int64_t), st));
-    return 0;
-  }
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && workspace && nnz_device,
-             "projection_2dgs_packed_count: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0,
-             "projection_2dgs_packed_count: quats must be 16-B aligned");
-  ProjFwdArgs a{C, N, width, height, near_plane, far_plane, radius_clip, means, quats, scales,
-                viewmats, Ks};
-  a.block_cnt = reinterpret_cast<int64_t *>(workspace);
-  const dim3 grid((N + 255) / 256, C);
-  hipLaunchKernelGGL(proj_fwd_kernel<1>, grid, dim3(256), 0, st, a);
-  gs::launch_packed_scan((int64_t)grid.x * grid.y, a.block_cnt, nnz_device, st);
-  GS_CHECK_LAUNCH("projection_2dgs_packed_count");
-  return 0;
-}
-
-extern "C" int gsplat_hip_projection_2dgs_packed_fwd(
-    int C, int N, const float *means, const float *quats, const float *scales,
-    const float *viewmats, const float *Ks, int width, int height, float near_plane,
-    float far_plane, float radius_clip, const void *workspace, int64_t *camera_ids,
-    int64_t *gaussian_ids, int32_t *radii, float *means2d, float *depths, float *ray_transforms,
-    float *normals, void *stream) {
-  GS_REQUIRE(C >= 0 && N >= 0, "projection_2dgs_packed_fwd: negative sizes C=%d N=%d", C, N);
-  if (C == 0 || N == 0) return 0;
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && workspace && camera_ids &&
-                 gaussian_ids && radii && means2d && depths && ray_transforms && normals,
-             "projection_2dgs_packed_fwd: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)means2d & 7) == 0,
-             "projection_2dgs_packed_fwd: quats must be 16-B aligned, means2d 8-B aligned");
-  ProjFwdArgs a{C, N, width, height, near_plane, far_plane, radius_clip, means, quats, scales,
-                viewmats, Ks, radii, means2d, depths, ray_transforms, normals};
-  a.block_off = reinterpret_cast<const int64_t *>(workspace);
-  a.camera_ids = camera_ids;
-  a.gaussian_ids = gaussian_ids;
-  hipLaunchKernelGGL(proj_fwd_kernel<2>, dim3((N + 255) / 256, C), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  GS_CHECK_LAUNCH("projection_2dgs_packed_fwd");
-  return 0;
-}
-
-// projection_2dgs_packed_bwd (Projection2DGSPacked.cu:274-420): one lane per
-// packed entry; dense [N, .] gradients by atomics, or (sparse_grad) one row
-// per entry for the COO gradients of _wrapper.py:1529-1570.  v_viewmats, as
-// in the reference, is not differentiated (zeros).
-extern "C" int gsplat_hip_projection_2dgs_packed_bwd(
-    int C, int N, int64_t nnz, const float *means, const float *quats, const float *scales,
-    const float *viewmats, const float *Ks, int width, int height, const int64_t *camera_ids,
-    const int64_t *gaussian_ids, const float *ray_transforms, const float *v_means2d,
-    const float *v_depths, const float *v_normals, const float *v_ray_transforms,
-    int sparse_grad, float *v_means, float *v_quats, float *v_scales, float *v_viewmats,
-    void *stream) {
-  (void)width;
-  (void)height;
-  GS_REQUIRE(C >= 0 && N >= 0 && nnz >= 0, "projection_2dgs_packed_bwd: negative sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (v_viewmats && C > 0) GS_HIP(gs::zero_async(v_viewmats, sizeof(float) * 16 * C, st));
-  if (!sparse_grad && N > 0) {
-    GS_HIP(gs::zero_async(v_means, sizeof(float) * 3 * N, st));
-    GS_HIP(gs::zero_async(v_quats, sizeof(float) * 4 * N, st));
-    GS_HIP(gs::zero_async(v_scales, sizeof(float) * 3 * N, st));
-  }
-  if (nnz == 0) return 0;
-  GS_REQUIRE(means && quats && scales && viewmats && Ks && camera_ids && gaussian_ids &&
-                 ray_transforms && v_means2d && v_normals && v_ray_transforms && v_means &&
-                 v_quats && v_scales,
-             "projection_2dgs_packed_bwd: null pointer argument");
-  GS_REQUIRE(((uintptr_t)quats & 15) == 0 && ((uintptr_t)v_quats & 15) == 0,
-             "projection_2dgs_packed_bwd: quats / v_quats must be 16-B aligned");
-  ProjBwdArgs a{C, N, means, quats, scales, viewmats, Ks, nullptr, ray_transforms, v_means2d,
-                v_depths, v_normals, v_ray_transforms, v_means, v_quats, v_scales, 0};
-  a.camera_ids = camera_ids;
-  a.gaussian_ids = gaussian_ids;
-  a.nnz = nnz;
-  a.sparse = sparse_grad;
-  hipLaunchKernelGGL(proj_bwd_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, a);
-  GS_CHECK_LAUNCH("projection_2dgs_packed_bwd");
-  return 0;
-}
 
 extern "C" int gsplat_hip_rasterize_2dgs_supported_channels(int D) {
   return channels_supported(D) ? 1 : 0;
@@ -2062,7 +1524,7 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
   GS_REQUIRE(isect_offsets && render_colors && render_alphas && last_ids &&
                  (lean || (render_normals && render_distort && render_median && median_ids)),
              "rasterize_2dgs_fwd: null pointer argument");
-  GS_REQUIRE(!lean || (records && tile_size == 16 && fwd2_enabled()),
+  GS_REQUIRE(!lean || (records && tile_size == 16),
              "rasterize_2dgs_fwd: a colours-only render needs the record path (16x16 tiles, D <= %d)",
              kSRecMaxD);
   GS_REQUIRE(n_isects == 0 || (means2d && ray_transforms && colors && opacities && normals &&
@@ -2088,8 +1550,8 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
     a.xcd_runs = xcd_runs();
     if (a.xcd_runs) grid_t = (unsigned)((n_tiles + 31) / 32 * 32);
   }
-  // 16x16 tiles: two pixels per lane (fwd2_kernel)
-  const bool px2 = tile_size == 16 && fwd2_enabled();
+  // 16x16 tiles: two pixels per lane (one: 1.62 / 1.76 against 1.10 / 1.63 ms at M5)
+  const bool px2 = tile_size == 16;
   if (records) {  // scalar-operand records (gsplat_hip_rasterize_2dgs_pack_records)
     GS_REQUIRE(px2 && D <= kSRecMaxD, "rasterize_2dgs_fwd: records need 16x16 tiles, D <= %d",
                kSRecMaxD);
@@ -2098,7 +1560,7 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
     hipLaunchKernelGGL((fwd2s_kernel<n, true>), dim3(grid_t), dim3(128), 0, st, a, records); \
   else if (D == n)                                                                            \
     hipLaunchKernelGGL((fwd2s_kernel<n, false>), dim3(grid_t), dim3(128), 0, st, a, records);
-    GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4)
+    GS_SREC_CHANNELS(GS_CASE)
 #undef GS_CASE
     GS_CHECK_LAUNCH("rasterize_2dgs_fwd");
     return 0;
@@ -2118,7 +1580,7 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
 }
 
 extern "C" int gsplat_hip_rasterize_2dgs_record_floats(int D, int tile_size) {
-  return (tile_size == 16 && D >= 1 && D <= kSRecMaxD && fwd2_enabled()) ? srec::NF : 0;
+  return (tile_size == 16 && D >= 1 && D <= kSRecMaxD) ? srec::NF : 0;
 }
 
 extern "C" int gsplat_hip_rasterize_2dgs_pack_records(int64_t n_gaussians, int D,
@@ -2141,7 +1603,7 @@ extern "C" int gsplat_hip_rasterize_2dgs_pack_records(int64_t n_gaussians, int D
   if (D == n)                                                                                 \
     hipLaunchKernelGGL(pack_srec_kernel<n>, grid, dim3(256), 0, st, n_gaussians, means2d,     \
                        ray_transforms, opacities, normals, colors, depths, visible, records);
-  GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4)
+  GS_SREC_CHANNELS(GS_CASE)
 #undef GS_CASE
   GS_CHECK_LAUNCH("rasterize_2dgs_pack_records");
   return 0;
@@ -2170,11 +1632,12 @@ extern "C" int gsplat_hip_rasterize_2dgs_bwd(
   GS_REQUIRE(channels_supported(D), "rasterize_2dgs_bwd: unsupported channel count %d", D);
   GS_REQUIRE(tile_size * tile_size <= 256, "rasterize_2dgs_bwd: tile_size %d > 16", tile_size);
   const int absgrad = v_means2d_abs != nullptr;
-  // LEAN kernels (bwd2_kernel, 16x16 tiles, D <= 4) whenever no normal / distortion / median gradient is
-  // asked for (a colours-only forward, which writes no median ids, has only
-  // that backward)
-  const bool px2 = tile_size == 16 && bwd2_enabled();
-  const bool lean = px2 && D <= 4 && !v_render_normals && !v_render_distort && !v_render_median;
+  // LEAN kernels (bwd2_kernel, 16x16 tiles, D <= kSRecMaxD) whenever no normal
+  // / distortion / median gradient is asked for (a colours-only forward, which
+  // writes no median ids, has only that backward)
+  const bool px2 = tile_size == 16;
+  const bool lean =
+      px2 && D <= kSRecMaxD && !v_render_normals && !v_render_distort && !v_render_median;
   const int S = lean ? lean_stride(D, absgrad) : fields_stride(D, absgrad);
   const int64_t G = n_gaussians;
   GS_REQUIRE(workspace_bytes >= G * S * (int64_t)sizeof(float),
@@ -2215,57 +1678,62 @@ extern "C" int gsplat_hip_rasterize_2dgs_bwd(
     a.v_render_median = v_render_median;
     a.packed = (float *)workspace; a.S = S;
     const int waves = (tile_size * tile_size + 63) / 64;
-    // 16x16 tiles: two pixels per lane (bwd2_kernel)
+    auto launch = [&](auto kernel, int block, size_t lds) {
+      hipLaunchKernelGGL(kernel, dim3(grid_t), dim3(block), lds, st, a);
+    };
+    if (lean) {
 #define GS_CASE(n)                                                                            \
   if (D == n) {                                                                               \
     const size_t lds = (size_t)waves * 64 * Rec<n>::NF * sizeof(float);                       \
-    if (lean && absgrad)                                                                      \
-      hipLaunchKernelGGL((bwd2_kernel<n <= 4 ? n : 4, true, true>), dim3(grid_t), dim3(128), \
-                         lds / 2, st, a);                                                     \
-    else if (lean && (a.dbg & 77))                                                            \
-      hipLaunchKernelGGL((bwd2_kernel<n <= 4 ? n : 4, false, true, true>), dim3(grid_t),     \
-                         dim3(128), lds / 2, st, a);                                          \
-    else if (lean)                                                                            \
-      hipLaunchKernelGGL((bwd2_kernel<n <= 4 ? n : 4, false, true>), dim3(grid_t), dim3(128),\
-                         lds / 2, st, a);                                                     \
-    else if (px2 && absgrad)                                                                       \
-      hipLaunchKernelGGL((bwd2_kernel<n, true>), dim3(grid_t), dim3(128), lds / 2, st, a);    \
-    else if (px2)                                                                             \
-      hipLaunchKernelGGL((bwd2_kernel<n, false>), dim3(grid_t), dim3(128), lds / 2, st, a);   \
-    else if (absgrad)                                                                         \
-      hipLaunchKernelGGL((bwd_kernel<n, true>), dim3(grid_t), dim3(64 * waves), lds, st, a);  \
+    if (absgrad)                                                                              \
+      launch(bwd2_kernel<n, true, true>, 128, lds / 2);                                       \
+    else if (a.dbg & 77)                                                                      \
+      launch(bwd2_kernel<n, false, true, true>, 128, lds / 2);                                \
     else                                                                                      \
-      hipLaunchKernelGGL((bwd_kernel<n, false>), dim3(grid_t), dim3(64 * waves), lds, st, a); \
+      launch(bwd2_kernel<n, false, true>, 128, lds / 2);                                      \
   }
-    GS_SURFEL_CHANNELS(GS_CASE)
+      GS_SREC_CHANNELS(GS_CASE)
 #undef GS_CASE
+    } else {
+#define GS_CASE(n)                                                                            \
+  if (D == n) {                                                                               \
+    const size_t lds = (size_t)waves * 64 * Rec<n>::NF * sizeof(float);                       \
+    if (px2 && absgrad)                                                                       \
+      launch(bwd2_kernel<n, true>, 128, lds / 2);                                             \
+    else if (px2)                                                                             \
+      launch(bwd2_kernel<n, false>, 128, lds / 2);                                            \
+    else if (absgrad)                                                                         \
+      launch(bwd_kernel<n, true>, 64 * waves, lds);                                           \
+    else                                                                                      \
+      launch(bwd_kernel<n, false>, 64 * waves, lds);                                          \
+  }
+      GS_SURFEL_CHANNELS(GS_CASE)
+#undef GS_CASE
+    }
     GS_CHECK_LAUNCH("rasterize_2dgs_bwd");
   }
-  const dim3 grid((unsigned)((G + 255) / 256));
-#define GS_CASE(n)                                                                             \
-  if (D == n && lean) {                                                                        \
-    if (absgrad)                                                                               \
-      hipLaunchKernelGGL((unpack_kernel<n <= 4 ? n : 4, true, true>), grid, dim3(256), 0, st, G, \
-                         visible, (const float *)workspace, ray_transforms, v_means2d,         \
-                         v_ray_transforms, v_colors, v_depths, v_opacities, v_normals, v_densify,\
-                         v_means2d_abs);                                                       \
-    else                                                                                       \
-      hipLaunchKernelGGL((unpack_kernel<n <= 4 ? n : 4, false, true>), grid, dim3(256), 0, st, G,\
-                         visible, (const float *)workspace, ray_transforms, v_means2d,         \
-                         v_ray_transforms, v_colors, v_depths, v_opacities, v_normals, v_densify,\
-                         v_means2d_abs);                                                       \
-  } else if (D == n) {                                                                         \
-    if (absgrad)                                                                               \
-      hipLaunchKernelGGL((unpack_kernel<n, true>), grid, dim3(256), 0, st, G, visible, (const float *)workspace, \
-                         ray_transforms, v_means2d, v_ray_transforms, v_colors, v_depths, v_opacities,\
-                         v_normals, v_densify, v_means2d_abs);                                 \
-    else                                                                                       \
-      hipLaunchKernelGGL((unpack_kernel<n, false>), grid, dim3(256), 0, st, G, visible, (const float *)workspace, \
-                         ray_transforms, v_means2d, v_ray_transforms, v_colors, v_depths, v_opacities,\
-                         v_normals, v_densify, v_means2d_abs);                                 \
-  }
-  GS_SURFEL_CHANNELS(GS_CASE)
+  auto unpack = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, G, visible,
+                       (const float *)workspace, ray_transforms, v_means2d, v_ray_transforms,
+                       v_colors, v_depths, v_opacities, v_normals, v_densify, v_means2d_abs);
+  };
+  if (lean) {
+#define GS_CASE(n)                            \
+  if (D == n && absgrad)                      \
+    unpack(unpack_kernel<n, true, true>);     \
+  else if (D == n)                            \
+    unpack(unpack_kernel<n, false, true>);
+    GS_SREC_CHANNELS(GS_CASE)
 #undef GS_CASE
+  } else {
+#define GS_CASE(n)                      \
+  if (D == n && absgrad)                \
+    unpack(unpack_kernel<n, true>);     \
+  else if (D == n)                      \
+    unpack(unpack_kernel<n, false>);
+    GS_SURFEL_CHANNELS(GS_CASE)
+#undef GS_CASE
+  }
   GS_CHECK_LAUNCH("rasterize_2dgs_unpack");
   return 0;
 }

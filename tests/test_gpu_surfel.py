@@ -119,15 +119,39 @@ def _oracle_fwd(sc, masks=None):
 def test_raster2dgs_fwd(seed, D, bg, C, thin):
     """thin: needle surfels, many edge-on -- the strip culling's ellipse test
     (surfel_keep) must never drop a contributing record."""
-    sc = surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, C=C, thin=thin)
+    _check_fwd(surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, C=C, thin=thin))
+
+
+def _check_fwd(sc, masks=None):
     assert len(sc["fids"]) > 200
-    _, _, _, (rc, ra, rn, rd, rm) = _raster_gpu(sc)
-    oc, oa, on, od, om, ol, omi = _oracle_fwd(sc)
+    _, _, _, (rc, ra, rn, rd, rm) = _raster_gpu(sc, masks=masks)
+    oc, oa, on, od, om, ol, omi = _oracle_fwd(sc, masks=masks)
     close_most(rc, oc, 1e-4, 1e-4, "colors", max_frac=5e-3)
     close_most(ra, oa, 1e-4, 1e-4, "alphas", max_frac=5e-3)
     close_most(rn, on, 1e-4, 1e-4, "normals", max_frac=5e-3)
     close_most(rd, od, 1e-3, 1e-3, "distort", max_frac=5e-3)
     close_most(rm, om, 1e-4, 1e-4, "median", max_frac=5e-3)
+
+
+@pytest.mark.parametrize("ts,seed,D,bg,C,thin", [(8, 5, 4, True, 1, False), (8, 6, 3, False, 2, True),
+                                                 (12, 5, 4, True, 1, False),
+                                                 (12, 3, 8, True, 1, True)])
+def test_raster2dgs_fwd_one_pixel_per_lane(ts, seed, D, bg, C, thin):
+    """Every tile size but 16 runs fwd_kernel (one pixel per lane), which the
+    16x16 scenes above never launch.  8: one full wave per tile.  12: 144
+    pixels, three waves, the last one partial (lanes past ts*ts are outside,
+    and each wave culls against its own rows' rectangle).  Comparisons and
+    bounds of test_raster2dgs_fwd."""
+    _check_fwd(surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, C=C, thin=thin, ts=ts))
+
+
+def test_raster2dgs_fwd_one_pixel_per_lane_masks():
+    """fwd_kernel's masked tiles: background or zero colours, everything else
+    zero (the oracle's definition), all five outputs."""
+    sc = surfel_scene(5, N=300, W=70, H=52, D=4, bg=True, ts=8)
+    masks = np.random.default_rng(0).random(sc["off"].shape) > 0.4
+    assert masks.any() and not masks.all()
+    _check_fwd(sc, masks=masks)
 
 
 @pytest.mark.parametrize("seed,D,bg,C,thin,masked", [(0, 4, True, 1, False, False),
@@ -139,8 +163,9 @@ def test_raster2dgs_fwd_records_bit_identical(monkeypatch, seed, D, bg, C, thin,
     """The scalar-operand record forward (csrc/surfel.hip fwd2s_kernel,
     GSPLAT_HIP_SURFEL_SREC=1) renders what the LDS-queue forward renders: the
     same per-pixel arithmetic on the same record values, up to the
-    compiler's FMA contraction of a few expressions (3.6e-7 seen in one of
-    the five outputs); the backward, which reads the forward's outputs and
+    compiler's FMA contraction of a few expressions (largest difference seen
+    over these cases: colours 4.3e-6, normals 3.6e-6, distortion 3.2e-6,
+    alphas 1.8e-6, median 0); the backward, which reads the forward's outputs and
     last / median ids, agrees to the order of its float atomics."""
     from gsplat_hip import _lib, _wrapper_2dgs
     assert _lib.query("gsplat_hip_rasterize_2dgs_record_floats", D, 16) == 32
@@ -222,7 +247,22 @@ def test_raster2dgs_fwd_masks():
                                                     (6, 9, True, True, False),
                                                     (7, 4, True, False, True)])
 def test_raster2dgs_bwd(seed, D, bg, absgrad, thin):
-    sc = surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, thin=thin)
+    _check_bwd(surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, thin=thin), seed, bg, absgrad)
+
+
+@pytest.mark.parametrize("ts,seed,D,bg,absgrad,thin", [(8, 0, 4, True, False, False),
+                                                       (8, 7, 4, True, True, True),
+                                                       (12, 1, 3, False, False, False),
+                                                       (12, 6, 9, True, True, False)])
+def test_raster2dgs_bwd_one_pixel_per_lane(ts, seed, D, bg, absgrad, thin):
+    """bwd_kernel (one pixel per lane: every tile size but 16), as
+    test_raster2dgs_fwd_one_pixel_per_lane; comparisons and bounds of
+    test_raster2dgs_bwd."""
+    _check_bwd(surfel_scene(seed, N=300, W=70, H=52, D=D, bg=bg, thin=thin, ts=ts), seed, bg,
+               absgrad)
+
+
+def _check_bwd(sc, seed, bg, absgrad):
     leaves, bgt, densify, outs = _raster_gpu(sc, absgrad=absgrad)
     rng = np.random.default_rng(seed + 100)
     vs = [rng.standard_normal(o.shape).astype(np.float32) for o in outs]

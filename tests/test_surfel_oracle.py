@@ -80,7 +80,7 @@ def test_proj2dgs_bwd_golden_exact_part():
 
 
 # ---------------------------------------------------------------- raster ---
-def surfel_scene(seed=0, N=60, W=40, H=36, D=4, bg=True, C=1, thin=False):
+def surfel_scene(seed=0, N=60, W=40, H=36, D=4, bg=True, C=1, thin=False, ts=16):
     rng = np.random.default_rng(seed)
     means = (rng.standard_normal((N, 3)) * [0.5, 0.5, 0.3] + [0, 0, 3]).astype(np.float32)
     quats = rng.standard_normal((N, 4)).astype(np.float32)
@@ -92,7 +92,6 @@ def surfel_scene(seed=0, N=60, W=40, H=36, D=4, bg=True, C=1, thin=False):
     vm[:, 0, 3] = np.arange(C) * 0.1
     K = np.tile(np.array([[60.0, 0, W / 2], [0, 60.0, H / 2], [0, 0, 1]], np.float32), (C, 1, 1))
     radii, m2, depths, rt, nr = S.proj2dgs_fwd(means, quats, scales, vm, K, W, H)
-    ts = 16
     tw, th = math.ceil(W / ts), math.ceil(H / ts)
     _, ids, fids = O.isect_tiles(m2, radii, depths, ts, tw, th)
     off = O.isect_offset_encode(ids, C, tw, th)
@@ -178,7 +177,17 @@ def torch_raster2dgs(m2, rt, colors, opac, nr, bg, W, H, ts, off, fids):
 
 @pytest.mark.parametrize("seed,bg", [(0, True), (1, False)])
 def test_raster2dgs_oracle_fwd_matches_torch(seed, bg):
-    sc = surfel_scene(seed, bg=bg)
+    _oracle_fwd_matches_torch(surfel_scene(seed, bg=bg))
+
+
+@pytest.mark.parametrize("seed,bg,ts", [(0, True, 8), (1, False, 12)])
+def test_raster2dgs_oracle_fwd_matches_torch_small_tiles(seed, bg, ts):
+    """The tile sizes at which tests/test_gpu_surfel.py holds the
+    one-pixel-per-lane kernels to the oracle."""
+    _oracle_fwd_matches_torch(surfel_scene(seed, bg=bg, ts=ts))
+
+
+def _oracle_fwd_matches_torch(sc):
     oc, oa, on, od, om, ol, omi = S.raster2dgs_fwd(
         sc["m2"], sc["rt"], sc["colors"], sc["opac"], sc["nr"], sc["bg"], None, sc["W"], sc["H"],
         sc["ts"], sc["off"], sc["fids"])
