@@ -28,6 +28,7 @@ from .compression import PngCompression
 from .depth_loss import sparse_depth_loss
 from .io import load_ply, save_ply
 from .losses import geometry_loss_2dgs
+from .mesh import TSDFVolume, save_mesh_ply
 from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
 from .undistort import remap_bilinear, undistort_images
@@ -66,5 +67,7 @@ __all__ = [
     "remap_bilinear",
     "save_ply",
     "load_ply",
+    "TSDFVolume",
+    "save_mesh_ply",
 ]
 __version__ = "0.1.0"

@@ -228,6 +228,13 @@ _SIGS = {
     "gsplat_hip_ply_count": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_ply_pack": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_ply_unpack": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gsplat_hip_tsdf_integrate": (_i32, [_i32, _i32, _i32, _f, _f, _f, _f, _i32, _i32, _i32, _p,
+                                         _p, _p, _p, _p, _f, _f, _f, _p, _i64, _i32, _p]),
+    "gsplat_hip_mc_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "gsplat_hip_mc_count": (_i32, [_i32, _i32, _i32, _p, _p, _f, _p, _p, _p]),
+    "gsplat_hip_mc_emit": (_i32, [_i32, _i32, _i32, _f, _f, _f, _f, _p, _p, _i64, _p, _i64, _i64,
+                                  _p, _p, _p, _p]),
+    "gsplat_hip_mc_table": (_i32, [_p]),
     "gsplat_hip_watchdog_arm": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
     "gsplat_hip_watchdog_beat": (_i32, [ctypes.c_char_p]),
     "gsplat_hip_watchdog_set_fallback": (_i32, [_i32, ctypes.c_char_p, _i32]),

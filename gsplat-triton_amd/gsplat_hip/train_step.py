@@ -284,6 +284,7 @@ _REFUSALS = {
                                 ("packed", "sparse_grad") + _MANY),
     "compression": ("one-GPU trainers only", _MANY),
     "checkpoint": ("one-GPU trainers only", _MANY),
+    "mesh": ("one-GPU trainers only", _MANY),
 }
 
 
@@ -1567,6 +1568,120 @@ class Trainer:
             os.path.getsize(os.path.join(compress_dir, f)) for f in os.listdir(compress_dir)
             if os.path.isfile(os.path.join(compress_dir, f)))
         return out
+
+    # ---------------------------------------------------------------- mesh
+    @torch.no_grad()
+    def extract_mesh(self, voxel_size=None, resolution=256, bounds=None, sdf_trunc=None,
+                     depth_trunc=None, depth_mode="median", alpha_min=0.5, cameras=None,
+                     camera_batch=8, colors=True, min_weight=0.0, path=None,
+                     max_voxels=1 << 30):
+        """The surface of the current Gaussians as a triangle mesh: the
+        training cameras (or the pool indices `cameras`) rendered
+        `camera_batch` at a time through the public rasterization_2dgs /
+        rasterization ("RGB+ED"), their z-depth fused into a TSDF volume and
+        marching cubes at 0 (mesh.TSDFVolume).  Returns (vertices [V,3],
+        faces [F,3] int32, colors [V,3] or None) on the device and writes
+        them to `path` (mesh.save_mesh_ply) when given.
+
+        depth_mode: "median" (2DGS only: render_median) or "expected"
+        bounds:     (lo, hi), three numbers each; None: the box of the means
+                    between the per-axis 1 % and 99 % quantiles, grown by
+                    sdf_trunc
+        voxel_size: None: the longest side of the bounds is `resolution` cells
+        sdf_trunc:  None: 5 voxel_size;  depth_trunc: None: no limit
+        A trainer with masks zeroes alpha outside each image's mask, so those
+        pixels are not fused.  app_opt: geometry only (colors=False).  The
+        parameters, the optimizer state and a captured step are not touched."""
+        name = "extract_mesh"
+        _refuse("mesh", {"gaussian_shard": self.gshard, "sharded_optimizer": bool(self.sharded),
+                         "world_size": self.world_size != 1}, name=name + " (mesh)")
+        if self.app_opt and colors:
+            raise NotImplementedError(f"{name}: app_opt colours depend on the image's embedding; "
+                                      "pass colors=False for the geometry alone")
+        if depth_mode not in ("median", "expected"):
+            raise ValueError(f"{name}: depth_mode 'median' or 'expected', got {depth_mode!r}")
+        if depth_mode == "median" and self.model != "2dgs":
+            raise ValueError(f"{name}: the 3DGS model renders the expected depth only; pass "
+                             "depth_mode='expected'")
+        camera_batch, max_voxels = int(camera_batch), int(max_voxels)
+        if camera_batch < 1:
+            raise ValueError(f"{name}: camera_batch must be >= 1, got {camera_batch}")
+        if voxel_size is not None and not float(voxel_size) > 0.0:
+            raise ValueError(f"{name}: voxel_size must be positive, got {voxel_size!r}")
+        if sdf_trunc is not None and not float(sdf_trunc) > 0.0:
+            raise ValueError(f"{name}: sdf_trunc must be positive, got {sdf_trunc!r}")
+        if voxel_size is None and int(resolution) <= (
+                10 if bounds is None and sdf_trunc is None else 0):
+            raise ValueError(f"{name}: resolution {resolution!r} leaves no cells")
+        if bounds is not None:
+            lo, hi = ([float(v) for v in b] for b in bounds)
+            if len(lo) != 3 or len(hi) != 3 or not all(a <= b for a, b in zip(lo, hi)):
+                raise ValueError(f"{name}: bounds must be (lo, hi) of three numbers, lo <= hi")
+        idx = list(range(len(self.viewmats))) if cameras is None else [int(c) for c in cameras]
+        if any(not 0 <= c < len(self.viewmats) for c in idx):
+            raise ValueError(f"{name}: cameras must index the {len(self.viewmats)} training "
+                             "cameras")
+        from .mesh import TSDFVolume, save_mesh_ply
+        self.sync()
+        p = {k: v.detach() for k, v in self.params.items()}
+        if bounds is None:
+            n = p["means"].shape[0]
+            ks = (max(1, math.ceil(0.01 * n)), max(1, math.ceil(0.99 * n)))
+            q = [[float(p["means"][:, a].kthvalue(k).values) for a in range(3)] for k in ks]
+            lo, hi = q
+            grow = sdf_trunc
+        else:
+            grow = 0.0
+        side = max(b - a for a, b in zip(lo, hi))
+        if voxel_size is None:
+            # side + 2 grow = resolution cells, with grow = sdf_trunc = 5 cells by default
+            h = (side / (int(resolution) - 10) if grow is None
+                 else (side + 2.0 * float(grow)) / int(resolution))
+            if not h > 0.0:
+                raise ValueError(f"{name}: the bounds are empty: pass voxel_size")
+        else:
+            h = float(voxel_size)
+        trunc = 5.0 * h if sdf_trunc is None else float(sdf_trunc)
+        grow = trunc if grow is None else float(grow)
+        lo, hi = [a - grow for a in lo], [b + grow for b in hi]
+        dims = [int(math.ceil((b - a) / h - 1e-6)) + 1 for a, b in zip(lo, hi)]
+        if dims[0] * dims[1] * dims[2] > max_voxels:
+            raise ValueError(f"{name}: a volume of {dims} grid points is more than max_voxels="
+                             f"{max_voxels}; pass a larger voxel_size or tighter bounds")
+        vol = TSDFVolume(lo, h, dims, sdf_trunc=trunc, device=self.device, colors=bool(colors))
+        scales, opac = torch.exp(p["scales"]), torch.sigmoid(p["opacities"])
+        for a in range(0, len(idx), camera_batch):
+            ids = torch.tensor(idx[a:a + camera_batch], device=self.device)
+            vms, Ks = self.viewmats.index_select(0, ids), self.Ks.index_select(0, ids)
+            if self.model == "2dgs":
+                out = rasterization_2dgs(p["means"], p["quats"], scales, opac,
+                                         (p["sh0"], p["shN"]), vms, Ks, self.width, self.height,
+                                         sh_degree=self.sh_degree, packed=False, near_plane=0.01,
+                                         far_plane=1e10, render_mode="RGB+ED",
+                                         depth_mode=depth_mode)
+                rgbd, alphas, median = out[0], out[1], out[5]
+                depth = median if depth_mode == "median" else rgbd[..., 3:4]
+            else:
+                if self.app_opt:  # geometry only: any colours do
+                    coeffs, deg = p["colors"], None
+                else:
+                    coeffs, deg = (p["sh0"], p["shN"]), self.sh_degree
+                rgbd, alphas, _ = rasterization(p["means"], p["quats"], scales, opac, coeffs, vms,
+                                                Ks, self.width, self.height, sh_degree=deg,
+                                                packed=False, near_plane=0.01, far_plane=1e10,
+                                                rasterize_mode=self.rasterize_mode,
+                                                render_mode="RGB+ED")
+                depth = rgbd[..., 3:4]
+            if self.masks is not None:
+                alphas = alphas * self.masks.index_select(0, ids)[..., None].to(alphas.dtype)
+            vol.integrate(depth.contiguous(), _wrapper._f32c(vms), _wrapper._f32c(Ks),
+                          colors=rgbd[..., :3].contiguous() if colors else None, alphas=alphas,
+                          depth_trunc=math.inf if depth_trunc is None else float(depth_trunc),
+                          alpha_min=alpha_min)
+        mesh = vol.extract_mesh(min_weight=min_weight)
+        if path is not None:
+            save_mesh_ply(path, *mesh)
+        return mesh
 
     # ---------------------------------------------------------- persistence
     def save_checkpoint(self, path, step: int):

@@ -68,7 +68,9 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_kmeans_update_workspace_bytes (splat compression);
  *     gsplat_hip_ply_count / _pack / _unpack / _workspace_bytes (PLY rows);
  *     gsplat_hip_l1_ssim_loss_masked_fwd / _bwd (the 3DGS trainer's per-image
- *     masks and random background, composed in the loss kernel). */
+ *     masks and random background, composed in the loss kernel);
+ *     gsplat_hip_tsdf_integrate, gsplat_hip_mc_count / _emit / _table /
+ *     _workspace_bytes (mesh export). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1436,6 +1438,60 @@ int gsplat_hip_ply_pack(int64_t n, int K1, const float *means, const float *scal
 int gsplat_hip_ply_unpack(int64_t n, int K1, int F, const float *rows, const int32_t *cols,
                           float *means, float *scales, float *quats, float *opacities,
                           float *sh0, float *shN, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Mesh export (ABI 38, new entries only; csrc/tsdf.hip): TSDF fusion of
+ * rendered z-depth and marching cubes at isovalue 0.  The volume is a dense
+ * grid of (nx, ny, nz) grid points, point (i, j, k) at origin + voxel_size *
+ * (i, j, k), arrays [nz, ny, nx] with x fastest, float32.  Up to 2^36 points;
+ * every linear index is 64-bit.  No atomics: bit-identical between calls.
+ *
+ * _tsdf_integrate: fuses C cameras in index order in one launch (the same bits
+ *   as C launches of one camera).  state: the planes tsdf, weight and, with
+ *   with_colors != 0, r, g, b, `plane_stride` floats apart (a multiple of 4,
+ *   >= nx ny nz; state 16-B aligned; the floats of a plane past nx ny nz are
+ *   read and written back unchanged).  depths[C,H,W], colors[C,H,W,3] (iff
+ *   with_colors), alphas[C,H,W] or NULL, viewmats[C,4,4] (world to camera),
+ *   Ks[C,3,3].  Per (voxel, camera): p_c = R p + t, skipped unless z > 0;
+ *   pixel (floor(fx x/z + cx), floor(fy y/z + cy)), skipped outside the image;
+ *   d = depths at it, skipped unless 0 < d <= depth_trunc and (alphas given)
+ *   alpha >= alpha_min; sdf = d - z, skipped if sdf < -sdf_trunc; otherwise
+ *   s = min(1, sdf / sdf_trunc), w1 = w + 1, tsdf = (tsdf w + s) / w1, every
+ *   colour plane by the same running mean, w = w1.
+ * _mc_count / _mc_emit: an indexed mesh.  A grid point is inside iff
+ *   tsdf < 0; a cell is valid iff its 8 corner weights are > min_weight.  Each
+ *   grid point owns its +x, +y, +z edges; an edge carries a vertex iff its
+ *   ends differ in sign and one of the up to 4 cells around it is valid.
+ *   Vertices are ordered by (owner's linear index, axis), faces by (cell's
+ *   linear index, triangle number in the case table).  A vertex is
+ *   pa + t (pb - pa) with t = va / (va - vb), a the owner; colours likewise.
+ *   Normals point towards positive tsdf.
+ *   _mc_workspace_bytes: of uninitialised memory, 16-B aligned.
+ *   _mc_count: fills the workspace and totals_device[2] (8-B aligned): the
+ *            vertex and the face count.
+ *   _mc_emit: after _mc_count on the same volume, with the totals read back
+ *            (n_vertices < 2^31): vertices[n_vertices,3], faces[n_faces,3]
+ *            (int32), and with colors (3 planes color_stride floats apart)
+ *            vertex_colors[n_vertices,3]; both NULL without.
+ * _mc_table: the case table the kernels were compiled with, out[256 * 16]
+ *   (host memory): per sign case (bit c = x + 2y + 4z set iff corner c is
+ *   inside) up to 5 triangles of cube edges, -1 after the last.  Edge
+ *   e = 4 axis + r runs along `axis` from the corner whose other two
+ *   coordinates are (r & 1, r >> 1).  Generated by tools/gen_mc_table.py. */
+int gsplat_hip_tsdf_integrate(int nx, int ny, int nz, float ox, float oy, float oz,
+                              float voxel_size, int C, int H, int W, const float *depths,
+                              const float *colors, const float *alphas, const float *viewmats,
+                              const float *Ks, float sdf_trunc, float depth_trunc,
+                              float alpha_min, float *state, int64_t plane_stride,
+                              int with_colors, void *stream);
+int64_t gsplat_hip_mc_workspace_bytes(int nx, int ny, int nz);
+int gsplat_hip_mc_count(int nx, int ny, int nz, const float *tsdf, const float *weight,
+                        float min_weight, void *workspace, int64_t *totals_device, void *stream);
+int gsplat_hip_mc_emit(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size,
+                       const float *tsdf, const float *colors, int64_t color_stride,
+                       const void *workspace, int64_t n_vertices, int64_t n_faces,
+                       float *vertices, float *vertex_colors, int32_t *faces, void *stream);
+int gsplat_hip_mc_table(int8_t *out);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
