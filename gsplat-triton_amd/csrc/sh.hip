@@ -61,6 +61,17 @@ GS_INLINE void fused_dir(const Fused &fz, int64_t i, float &x, float &y, float &
   fused_dir_cg(fz, c, i - c * fz.N, x, y, z);
 }
 
+// sh + 0.5, the argument of the output clamp and of its backward gate, as a
+// separate rounded addition: at degree 0 `B[0] * c + 0.5f` would contract
+// into one fma in the forward and the unstaged backward but not in the staged
+// backward (whose sum starts from 0), and the three would then disagree on
+// rows with fl(B[0] * c) == -0.5 -- colour 0 and the gate open, as
+// torch.clamp_min(sh + 0.5, 0), in all of them this way.
+GS_INLINE float gate_arg(float sh) {
+#pragma clang fp contract(off)
+  return sh + 0.5f;
+}
+
 template <int DEG, bool FUSED>
 __global__ void __launch_bounds__(256)
 sh_fwd_kernel(int64_t n, int64_t n_coeff_rows, Coeffs cf, const float *__restrict__ dirs,
@@ -99,9 +110,9 @@ sh_fwd_kernel(int64_t n, int64_t n_coeff_rows, Coeffs cf, const float *__restric
     b += B[k] * pr[3 * (k - 1) + 2];
   }
   if (FUSED) {
-    r = fmaxf(r + 0.5f, 0.f);
-    g = fmaxf(g + 0.5f, 0.f);
-    b = fmaxf(b + 0.5f, 0.f);
+    r = fmaxf(gate_arg(r), 0.f);
+    g = fmaxf(gate_arg(g), 0.f);
+    b = fmaxf(gate_arg(b), 0.f);
   }
   o[0] = r; o[1] = g; o[2] = b;
 }
@@ -151,9 +162,9 @@ sh_bwd_kernel(int64_t n, int K, int64_t n_coeff_rows, Coeffs cf, const float *__
       g += B[k] * pr[3 * (k - 1) + 1];
       b += B[k] * pr[3 * (k - 1) + 2];
     }
-    vr = (r + 0.5f >= 0.f) ? vr : 0.f;
-    vg = (g + 0.5f >= 0.f) ? vg : 0.f;
-    vb = (b + 0.5f >= 0.f) ? vb : 0.f;
+    vr = (gate_arg(r) >= 0.f) ? vr : 0.f;
+    vg = (gate_arg(g) >= 0.f) ? vg : 0.f;
+    vb = (gate_arg(b) >= 0.f) ? vb : 0.f;
   }
   v0[0] = B[0] * vr; v0[1] = B[0] * vg; v0[2] = B[0] * vb;
 #pragma unroll
@@ -377,9 +388,9 @@ sh_bwd_staged_kernel(int64_t n, Coeffs cf, const float *__restrict__ dirs,
           g += B[k] * coef(k, 1);
           b += B[k] * coef(k, 2);
         }
-        vr = (r + 0.5f >= 0.f) ? vr : 0.f;
-        vg = (g + 0.5f >= 0.f) ? vg : 0.f;
-        vb = (b + 0.5f >= 0.f) ? vb : 0.f;
+        vr = (gate_arg(r) >= 0.f) ? vr : 0.f;
+        vg = (gate_arg(g) >= 0.f) ? vg : 0.f;
+        vb = (gate_arg(b) >= 0.f) ? vb : 0.f;
       }
       if (want_dirs) {
         float vx = 0.f, vy = 0.f, vz = 0.f;

@@ -1,7 +1,9 @@
 """GPU parity: the HIP path (through the C ABI) against the reference goldens
 and the CPU oracle.  Tolerances follow the reference's own tests
 (triton_tests/test_fused_proj.py:116-162, test_sh.py:25-37,
-test_isect.py:86-89 [exact], test_ras2pix.py:132-161)."""
+test_isect.py:86-89 [exact], test_ras2pix.py:132-161).
+The SH goldens here anchor the kernels to the reference at 1e-4; the float64
+bounds of every SH instantiation are in tests/test_gpu_sh_matrix.py."""
 
 import math
 
