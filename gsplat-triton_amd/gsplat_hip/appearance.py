@@ -18,11 +18,13 @@ gradients in a workspace) and app_reduce_adam (their ordered sum, and the
 reference's two Adam optimizers in place)."""
 
 import ctypes
+import math
 
 import torch
 
 from . import _lib
 from ._wrapper import _aligned16, _dev_check, _f32c, _ptr, _stream
+from .losses import SideOptimizer, adam_factors
 
 FEATURE_DIM = 32
 EMBED_DIM = 16
@@ -234,8 +236,8 @@ class _AppearanceColors(torch.autograd.Function):
 class _TrainerColors(torch.autograd.Function):
     """The training step's colours [1, N, 3] (Trainer(app_opt=True)): the
     forward kernel over the projection's radii, the backward kernel leaving the
-    head's and the embedding row's partial sums in the trainer's workspace
-    (Trainer._app_step sums them and steps the module's optimizers) and
+    head's and the embedding row's partial sums in the module's workspace
+    (AppearanceOptimizer.launch sums them and steps the module's optimizers) and
     handing dL/dmeans to the step's StepFusion, as the SH colours' backward
     does, so the projection backward's geometry Adam sees the whole gradient."""
 
@@ -295,3 +297,82 @@ def appearance_colors(features, base_colors, embeds, means, campos, head, sh_deg
     _dev_check(features, base_colors, embeds, means, campos, masks, *hd)
     return _AppearanceColors.apply(features, base_colors, embeds, means, campos, masks,
                                    int(sh_degree), *hd)
+
+
+class AppearanceOptimizer(SideOptimizer):
+    """Trainer(app_opt=True)'s module (utils.py AppearanceOptModule) and its two
+    Adam optimizers: `embeds` [n_images, 16], N(0,1); the head, one buffer `flat`
+    in the order W1, b1, W2, b2, W3, b3 with `head` its six views (torch's
+    default Linear initialisation, U(+-1/sqrt(fan_in)), the last layer zero);
+    both pairs of moments, the gradient buffer, the colour backward's workspace.
+    Every draw comes from a generator of its own.  `groups`: the initial
+    `features` U(0,1) [N,32] and logits `colors`, which the trainer takes as
+    groups of its own Adam (the rgbs clamped to [1/512, 1 - 1/512] first: the
+    reference's plain logit gives +-inf for pure black or white SfM points)."""
+
+    name = "app"
+
+    def __init__(self, n_images, rgbs, device, seed, lr, weight_decay, embed_dim, sh_degree):
+        if int(embed_dim) != 16:
+            raise ValueError("app_opt: app_embed_dim is fixed at 16 (the kernels' layout), "
+                             f"got {embed_dim!r}")
+        if int(sh_degree) != 3:
+            raise ValueError("app_opt: sh_degree is fixed at 3 (the module's 16 bases), "
+                             f"got {sh_degree!r}")
+        self.lr, self.weight_decay = float(lr), float(weight_decay)
+        g = torch.Generator().manual_seed(seed + 2027)
+        self.groups = {"features": torch.rand(rgbs.shape[0], FEATURE_DIM, generator=g),
+                       "colors": torch.logit(rgbs.float().clamp(1.0 / 512, 1.0 - 1.0 / 512))}
+        self.embeds = torch.randn(n_images, EMBED_DIM, generator=g).to(device)
+        flat = (torch.rand(HEAD_NUMEL, generator=g) * 2.0 - 1.0) * (1.0 / math.sqrt(WIDTH))
+        flat[2 * (WIDTH * WIDTH + WIDTH):] = 0.0
+        self.flat = flat.to(device)
+        self.head = [t.view(shape) for t, shape in zip(
+            self.flat.split([math.prod(shape) for shape in HEAD_SHAPES]), HEAD_SHAPES)]
+        self.head_moments = [torch.zeros_like(self.flat), torch.zeros_like(self.flat)]
+        self.embed_moments = [torch.zeros_like(self.embeds), torch.zeros_like(self.embeds)]
+        self.grads = torch.zeros(HEAD_NUMEL + EMBED_DIM, device=device)
+
+    def _workspace(self, n):
+        return app_workspace(n, 1, self.embeds.device)
+
+    def colors(self, params, viewmats, sh_degree, cam_index, fusion):
+        """rasterization(_app=...)'s callable: the colours [1,N,3] of the camera
+        `viewmats` [1,4,4] from the projection's radii (invisible Gaussians are
+        skipped), the embedding row of the device index `cam_index` (None: the
+        zero embedding of the reference's evaluation)."""
+        ws = self.prepare(params["means"].shape[0])
+        vm = viewmats.detach()
+        # the camera centre -R^T t, elementwise on the device
+        campos = -(vm[:, :3, :3] * vm[:, :3, 3:4]).sum(1)
+        return lambda radii: trainer_colors(
+            params["features"], params["colors"], params["means"], radii, campos, self.head,
+            sh_degree, None if cam_index is None else self.embeds, cam_index, ws, fusion)
+
+    def factors(self, it):
+        """torch's Adam for the head (lr) and the embedding table (10 x lr)."""
+        lrs = [self.lr, self.lr * EMBED_LR_MULT]
+        (sh, ib), (se, _) = adam_factors(lrs, BETAS, self.step_count + 1)
+        return sh, ib, se, 0.0
+
+    def launch(self, s, hyper):
+        """After the backward: the ordered sum of the colour backward's partial
+        sums and the module's two Adam optimizers in place (head: lr; the
+        embedding table: 10 x lr with app_opt_reg as weight decay, dense)."""
+        if hyper is None:
+            self.step_count += 1
+        app_reduce_adam(self.ws, self.ws_n, 1, self.grads, self.head, *self.head_moments,
+                        self.lr, self.step_count, embeds=self.embeds, embed_ids=s.cam,
+                        embed_exp_avg=self.embed_moments[0],
+                        embed_exp_avg_sq=self.embed_moments[1],
+                        embed_weight_decay=self.weight_decay, hyper=hyper, skip=s.void)
+
+    def moments(self):
+        return {"app_embeds": list(self.embed_moments), "app_head": list(self.head_moments)}
+
+    def checkpoint_tables(self):
+        return {"app_module": {"embeds.weight": self.embeds, **dict(zip(HEAD_KEYS, self.head))}}, {}
+
+    def state_dict(self):
+        """A copy under the reference module's keys: checkpoints interchange."""
+        return {k: t.detach().clone() for k, t in self.checkpoint_tables()[0]["app_module"].items()}

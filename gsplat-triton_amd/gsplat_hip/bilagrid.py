@@ -11,6 +11,7 @@ means Wg = X, Hg = Y, L = W.
     bilagrid_tv_loss(grids)                  total variation (a 0-d tensor)
     bilagrid_identity(num, shape, device)    the initial parameter
     bilagrid_lr(it, max_steps, base)         the reference's learning rate
+    BilateralGridOptimizer                   the trainer's grids and their Adam
 
 The pixel coordinates are implicit ((x + 0.5) / W, (y + 0.5) / H: the
 trainer's meshgrid), the guidance is the BT.601 gray of the pixel."""
@@ -22,6 +23,7 @@ import torch
 
 from . import _lib
 from ._wrapper import _dev_check, _f32c, _ptr, _stream
+from .losses import FusedAdam, SideOptimizer, adam_factors
 
 
 def _check_grids(grids):
@@ -209,3 +211,47 @@ def bilagrid_lr(it, max_steps, base=2e-3):
         return float(base)
     warm = 0.01 + 0.99 * min(int(it), 1000) / 1000.0
     return float(base) * warm * math.pow(0.01, int(it) / float(max_steps))
+
+
+class BilateralGridOptimizer(SideOptimizer):
+    """Trainer(bilateral_grid=True)'s `grids` [n_images, 12, L, Hg, Wg] and their
+    optimizer `opt` (simple_trainer.py:300-318): Adam(lr 2e-3 sqrt(BS), eps 1e-15)
+    stepped densely every step, its lr on the chained schedule (bilagrid_lr)."""
+
+    name = "bil"
+    TV_WEIGHT = 10.0  # simple_trainer.py:664: loss += 10 * tv
+
+    def __init__(self, n_images, shape, device, batch_size=1, max_steps=None):
+        self.shape = tuple(int(v) for v in shape)
+        if len(self.shape) != 3 or min(self.shape) < 2:
+            raise ValueError(f"bilateral_grid_shape: (X, Y, W), each >= 2, got {shape!r}")
+        self.grids = torch.nn.Parameter(bilagrid_identity(n_images, self.shape, device=device))
+        self.lr, self.max_steps = 2e-3 * math.sqrt(batch_size), max_steps
+        self.opt = FusedAdam([self.grids], [self.lr], betas=(0.9, 0.999), eps=1e-15)
+
+    step_count = property(lambda self: self.opt.step_count,  # (FusedAdam.step's own count)
+                          lambda self, n: setattr(self.opt, "step_count", n))
+
+    def slice_tv(self, colors, cam_index):
+        """(`colors` through the grid of the device index `cam_index`, TV_WEIGHT x
+        the grids' total variation): simple_trainer.py:620-630, 663-665."""
+        return _slice_tv(self.grids, colors, cam_index, self.TV_WEIGHT)
+
+    def factors(self, it):
+        """The grids' Adam: its own betas, the chained schedule's lr (set here)."""
+        self.opt.lrs[0] = bilagrid_lr(it, self.max_steps, self.lr)
+        return adam_factors(self.opt.lrs, self.opt.betas, self.opt.step_count + 1)[0]
+
+    def launch(self, s, hyper):
+        if hyper is None:
+            self.factors(s.it)  # (sets this step's learning rate)
+            self.opt.step()
+        else:
+            self.opt.step(hyper=hyper, void=s.void)
+        self.opt.zero_grad()
+
+    def moments(self):
+        return {"bil_grids": [self.opt.exp_avg[0], self.opt.exp_avg_sq[0]]}
+
+    def checkpoint_tables(self):
+        return {}, {"bil_grids": self.grids}

@@ -8,7 +8,7 @@ exactly.
                    (means scales quats opacities sh0 shN; app_opt: features,
                    colors instead of sh0 / shN)
     "pose_adjust"  {"embeds.weight": [n_img, 9]}            with pose_opt
-    "app_module"   Trainer.app_state_dict()                 with app_opt
+    "app_module"   AppearanceOptimizer.state_dict()         with app_opt
     "gsplat_hip"   everything else the next step reads that is neither a
                    constructor argument nor the dataset (the reference ignores
                    the key): format version, the Adam moments and step counts,
@@ -20,8 +20,8 @@ The file holds only CPU tensors, numbers, strings, lists and dicts, so it loads
 with `torch.load(weights_only=True)`.  Restoring goes the way Trainer.refine
 replaces its tensors (new Parameters, _load_moments, _register_hooks,
 _param_gen += 1: a captured step re-captures at its next step); tensors whose
-shape the constructor fixed (grids, pose and appearance tables and their
-moments) are copied in place.
+shape the constructor fixed are copied in place by their owners, Trainer.sides
+(losses.SideOptimizer names its tables and moments; none is named here).
 """
 
 import dataclasses
@@ -95,6 +95,8 @@ def _set_adam_step(tr, moments, step):
 
 
 def _cpu(t):
+    if isinstance(t, dict):
+        return {k: _cpu(v) for k, v in t.items()}
     return t.detach().to("cpu", copy=True).contiguous()
 
 
@@ -102,23 +104,20 @@ def state(tr, step) -> dict:
     """The checkpoint of `tr` after step `step` as a dict (module docstring)."""
     tr.sync()
     out = {"step": int(step), "splats": {k: _cpu(p) for k, p in tr.params.items()}}
-    if tr.pose_opt:
-        out["pose_adjust"] = {"embeds.weight": _cpu(tr.pose_embeds)}
-    if tr.app_opt:
-        out["app_module"] = {k: _cpu(v) for k, v in tr.app_state_dict().items()}
+    tables = [so.checkpoint_tables() for so in tr.sides]
+    for ref, _ in tables:
+        out.update(_cpu(ref))
     gs = {"format": FORMAT_VERSION, "fingerprint": fingerprint(tr),
           "moments": {k: [_cpu(m), _cpu(v)] for k, (m, v) in tr.moments().items()},
           "adam_step": _adam_step(tr),
-          "side_steps": {so.name: int(getattr(*so.counter)) for so in tr.side_opts},
+          "side_steps": {so.name: int(so.step_count) for so in tr.side_opts},
           "grad2d": _cpu(tr.grad2d), "count": _cpu(tr.count),
           "radii2d": None if tr.radii2d is None else _cpu(tr.radii2d),
           "refine_log": [[int(x) for x in row] for row in tr.refine_log],
           "rng": _cpu(tr.rng.get_state()), "noise_seed": str(int(tr._noise_seed)),
           "split": {k: _plain(getattr(tr, k, None)) for k in SPLIT_KEYS}}
-    if tr.bilateral_grid:
-        gs["bil_grids"] = _cpu(tr.bil_grids)
-    if tr.pose_active and tr.pose_noise_table is not None:
-        gs["pose_noise_table"] = _cpu(tr.pose_noise_table)
+    for _, own in tables:
+        gs.update(_cpu(own))
     out["gsplat_hip"] = gs
     return out
 
@@ -179,36 +178,15 @@ def _check_splats(tr, splats, who):
 def load_splats(tr, splats):
     """The Gaussians of `splats` (name -> tensor, e.g. load_ply's or
     PngCompression.decompress's) as the trainer's parameters: zero moments and
-    step count, fresh statistics (the evaluation path; a start for fine-tuning)."""
+    step count, fresh statistics (the evaluation path; a start for fine-tuning).
+    The side optimizers keep their tables, moments and step counts."""
     refuse(tr, "load_splats (checkpoint)")
     names = _check_splats(tr, splats, "load_splats")
     params = {k: splats[k].detach() for k in names}
     zeros = {k: [torch.zeros_like(v, dtype=torch.float32),
                  torch.zeros_like(v, dtype=torch.float32)] for k, v in params.items()}
-    if tr.bilateral_grid:
-        zeros["bil_grids"] = [tr.bil_opt.exp_avg[0], tr.bil_opt.exp_avg_sq[0]]
     _install(tr, params, zeros, 0)
     _fresh_statistics(tr)
-
-
-def _copy_side(tr, ck, zero_moments):
-    """pose_adjust / app_module into the trainer's tables, in place."""
-    if tr.pose_opt and "pose_adjust" in ck:
-        tr.pose_embeds.copy_(ck["pose_adjust"]["embeds.weight"])
-        if zero_moments:
-            tr._pose_m.zero_()
-            tr._pose_v.zero_()
-            tr.pose_step_count = 0
-    if tr.app_opt and "app_module" in ck:
-        from .appearance import HEAD_KEYS
-        sd = ck["app_module"]
-        tr.app_embeds.copy_(sd["embeds.weight"])
-        for k, t in zip(HEAD_KEYS, tr.app_head):
-            t.copy_(sd[k])
-        if zero_moments:
-            for t in (tr._app_head_m, tr._app_head_v, tr._app_embed_m, tr._app_embed_v):
-                t.zero_()
-            tr.app_step_count = 0
 
 
 @torch.no_grad()
@@ -229,7 +207,8 @@ def load(tr, paths, resume=True):
         # simple_trainer.py:1061-1062: the files' Gaussians concatenated
         splats = {k: torch.cat([ck["splats"][k] for ck in cks]) for k in cks[0]["splats"]}
         load_splats(tr, splats)
-        _copy_side(tr, cks[0], zero_moments=True)
+        for so in tr.sides:  # pose_adjust / app_module of the first: the reference's keys alone
+            so.load_checkpoint_tables(cks[0], {}, reset=True)
         return step
     ck = cks[0]
     gs = ck["gsplat_hip"]
@@ -239,32 +218,17 @@ def load(tr, paths, resume=True):
     _check_fingerprint(tr, gs["fingerprint"])
     names = _check_splats(tr, ck["splats"], "load_checkpoint")
     dev = tr.device
-    moments = {k: gs["moments"][k] for k in names}
-    if tr.bilateral_grid:
-        tr.sync()
-        tr.bil_grids.data.copy_(gs["bil_grids"])
-        moments["bil_grids"] = gs["moments"]["bil_grids"]
-    _install(tr, {k: ck["splats"][k] for k in names}, moments, gs["adam_step"])
-    _copy_side(tr, ck, zero_moments=False)
-    if tr.pose_opt:
-        tr._pose_m.copy_(gs["moments"]["pose_embeds"][0])
-        tr._pose_v.copy_(gs["moments"]["pose_embeds"][1])
-    if tr.app_opt:
-        tr._app_embed_m.copy_(gs["moments"]["app_embeds"][0])
-        tr._app_embed_v.copy_(gs["moments"]["app_embeds"][1])
-        tr._app_head_m.copy_(gs["moments"]["app_head"][0])
-        tr._app_head_v.copy_(gs["moments"]["app_head"][1])
+    _install(tr, {k: ck["splats"][k] for k in names}, gs["moments"], gs["adam_step"])
+    for so in tr.sides:  # (their moments went in with the Gaussians': Trainer._load_moments)
+        so.load_checkpoint_tables(ck, gs)
     for so in tr.side_opts:
-        obj, attr = so.counter
-        setattr(obj, attr, int(gs["side_steps"][so.name]))
+        so.step_count = int(gs["side_steps"][so.name])
     tr.grad2d = gs["grad2d"].to(dev)
     tr.count = gs["count"].to(dev)
     tr.radii2d = None if gs["radii2d"] is None else gs["radii2d"].to(dev)
     tr.refine_log = [tuple(row) for row in gs["refine_log"]]
     tr.rng.set_state(gs["rng"])
     tr._noise_seed = int(gs["noise_seed"])
-    if "pose_noise_table" in gs:
-        tr.pose_noise_table.copy_(gs["pose_noise_table"])
     for k, v in gs["split"].items():
         if v is not None or k in ("split_div", "split_threshold"):
             setattr(tr, k, v)
@@ -284,5 +248,5 @@ def save_ply(tr, path, sh_degree=None):
     deg = tr.sh_degree if sh_degree is None else int(sh_degree)
     zeros = torch.zeros_like(p["means"])
     colors = appearance_colors(p["features"], p["colors"], None, zeros,
-                               torch.zeros(1, 3, device=zeros.device), tr.app_head, deg)[0]
+                               torch.zeros(1, 3, device=zeros.device), tr.app.head, deg)[0]
     return _save_ply({k: p[k] for k in ("means", "scales", "quats", "opacities")}, path, colors)

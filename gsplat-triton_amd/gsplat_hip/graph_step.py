@@ -179,7 +179,7 @@ BLOCK = (
     # the Gaussians' Adam factors (lr / (1 - b1^t), 1 / sqrt(1 - b2^t)) per
     # launched group in launch order, then the SH-Adam's three (Trainer._layout)
     ("adam", 0, "float32", 56),
-    # the side optimizers' factors (train_step.SideOptimizer.name): the
+    # the side optimizers' factors (losses.SideOptimizer.name): the
     # appearance module's, the bilateral grids', the pose table's
     ("app", 224, "float32", 4),
     ("bil", 240, "float32", 2),
@@ -406,9 +406,8 @@ class GraphStep:
         _wrapper._timers = None  # no timing events inside the graph
         if self.dp:
             tr.opt.wait()  # an eager step's deferred all-gathers
-        for so in tr.side_opts:
-            if so.workspace is not None:
-                so.workspace()  # sized for the Gaussians, allocated outside the capture
+        for so in tr.side_opts:  # sized for the Gaussians, allocated outside the capture
+            so.prepare(tr.params["means"].shape[0])
         torch.cuda.synchronize(self.dev)
         self.ring_now = self.ring_loss and not any(self.terms)
         try:
@@ -571,7 +570,7 @@ class GraphStep:
         their factors from the block: the counts are kept here)."""
         self.tr.opt.step_count += n
         for so in self.tr.side_opts:
-            so.advance(n)
+            so.step_count += n
 
     def _issue(self, it, ret=None):
         """Replay step `it` as the `issued`-th step; returns its loss: the

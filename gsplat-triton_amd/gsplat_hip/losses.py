@@ -522,3 +522,54 @@ class FusedAdam:
     def zero_grad(self, set_to_none=True):
         for p in self.params:
             p.grad = None
+
+
+class SideOptimizer:
+    """An Adam beside the Gaussians' that owns its state (bilagrid.
+    BilateralGridOptimizer, pose.PoseOptimizer, appearance.AppearanceOptimizer),
+    launched after it in Trainer.side_opts' order.  A class sets `name`, its slot
+    in graph_step.BLOCK, and implements
+      factors(it)          that slot's floats for the step after step_count
+      launch(s, hyper)     the launch of step `s` (StepInputs); hyper None: the
+                           host's factors, counting the step itself (as
+                           FusedAdam.step does), else the slot's, the count being
+                           the caller's business
+      moments()            key -> [exp_avg, exp_avg_sq], the tensors themselves
+      checkpoint_tables()  (entries under the reference's keys, entries of the
+                           "gsplat_hip" block), the tables themselves
+      _workspace(n)        its workspace for n Gaussians, if it has one."""
+
+    name = None
+    optimised = True  # listed in Trainer.side_opts: launched, counted, its moments kept
+    step_count = 0
+    ws, ws_n = None, 0  # the workspace, sized for ws_n Gaussians
+
+    def _workspace(self, n):
+        return None
+
+    def prepare(self, n):
+        """The workspace for `n` Gaussians (a new size: not inside a capture)."""
+        if self.ws_n != n:
+            self.ws, self.ws_n = self._workspace(n), n
+        return self.ws
+
+    @torch.no_grad()
+    def load_moments(self, moments):
+        """Copies in those of `moments` (moments()'s keys) that are there."""
+        for k, mine in self.moments().items():
+            for dst, src in zip(mine, moments.get(k, ())):
+                dst.copy_(src)
+
+    @torch.no_grad()
+    def load_checkpoint_tables(self, ck, gs, reset=False):
+        """Copies in the tables that the file `ck` and its block `gs` carry;
+        `reset`: then zero moments and step count as well."""
+        hits = [(mine, src[key]) for src, tables in zip((ck, gs), self.checkpoint_tables())
+                for key, mine in tables.items() if key in src]
+        for mine, theirs in hits:  # a tensor, or a dict of tensors
+            for k, t in (mine.items() if isinstance(mine, dict) else [(None, mine)]):
+                t.copy_(theirs if k is None else theirs[k])
+        if hits and reset:
+            for t in sum(self.moments().values(), []):
+                t.zero_()
+            self.step_count = 0

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._wrapper import _dev_check, _f32c, _ptr, _stream
+from .losses import SideOptimizer, adam_factors
 
 BETAS = (0.9, 0.999)
 EPS = 1e-8
@@ -119,3 +120,63 @@ def pose_bwd_adam(workspace, N, base_viewmat, cam_index, embeds, exp_avg, exp_av
               ctypes.c_float(lr), ctypes.c_float(betas[0]), ctypes.c_float(betas[1]),
               ctypes.c_float(eps), ctypes.c_float(weight_decay), int(step), _ptr(hyper),
               _ptr(skip), _stream())
+
+
+class PoseOptimizer(SideOptimizer):
+    """Trainer(pose_opt / pose_noise)'s state: `embeds` [n_images, 9] (utils.py
+    CameraOptModule: embeds.weight, zero_init) with the moments of its Adam(lr
+    pose_opt_lr sqrt(BS), weight_decay pose_opt_reg), the fixed perturbation
+    `noise` (pose_perturb.random_init: N(0, pose_noise) from a generator of its
+    own, or None), the step's view matrix and the projection backward's
+    workspace.  `optimised` False (pose_noise alone): nothing is stepped."""
+
+    name = "pose"
+
+    def __init__(self, n_images, device, seed, optimised, noise_std, lr, weight_decay, max_steps):
+        self.optimised, self.max_steps = bool(optimised), max_steps
+        self.lr, self.weight_decay = float(lr), float(weight_decay)
+        self.embeds = torch.zeros(n_images, 9, device=device)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.embeds), torch.zeros_like(self.embeds)
+        self.noise = None
+        if noise_std > 0.0:
+            g = torch.Generator().manual_seed(seed + 1013)
+            self.noise = (torch.randn(n_images, 9, generator=g) * noise_std).to(device)
+        self.viewmat = torch.empty(1, 4, 4, device=device)  # the step's view matrix
+
+    def lr_at(self, it):
+        """The learning rate at step `it` (pose_lr on pose_opt_lr sqrt(BS))."""
+        return pose_lr(it, self.max_steps, self.lr)
+
+    def _workspace(self, n):
+        return pose_workspace(n, self.embeds.device)
+
+    def apply(self, base, cam_index, out=None):
+        """Launch (a): `base` [1,4,4] adjusted by the noise and embedding rows of
+        the device index `cam_index` into `out` (default: the step's buffer)."""
+        return pose_apply(base, cam_index, self.embeds if self.optimised else None, self.noise,
+                          out=self.viewmat if out is None else out)
+
+    def factors(self, it):
+        return adam_factors([self.lr_at(it)], BETAS, self.step_count + 1)[0]
+
+    def launch(self, s, hyper):
+        """Launch (c): the pose gradient from the projection backward's partials
+        and the pose Adam over the whole table."""
+        if not s.geom_applied:
+            raise RuntimeError("pose_opt: the projection backward did not run the geometry "
+                               "Adam, so it formed no pose gradient (a loss term outside the "
+                               "render reached the geometry parameters?)")
+        lr, step = 0.0, 1  # unused with the device factors
+        if hyper is None:
+            self.step_count += 1
+            lr, step = self.lr_at(s.it), self.step_count
+        pose_bwd_adam(self.ws, self.ws_n, _f32c(s.viewmats), s.cam, self.embeds, self.exp_avg,
+                      self.exp_avg_sq, lr, self.weight_decay, step, noise=self.noise, hyper=hyper,
+                      skip=s.void)
+
+    def moments(self):
+        return {"pose_embeds": [self.exp_avg, self.exp_avg_sq]}
+
+    def checkpoint_tables(self):
+        return ({"pose_adjust": {"embeds.weight": self.embeds}} if self.optimised else {},
+                {} if self.noise is None else {"pose_noise_table": self.noise})

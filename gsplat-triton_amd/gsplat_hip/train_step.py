@@ -13,7 +13,8 @@ call it with a StepInputs record saying where the step's inputs live -- host
 values and views of the step's camera, or views of the captured step's input
 block, its void flag and its rings.  The Adam optimizers beside the
 Gaussians' (the bilateral grids', the pose table's, the appearance module's)
-are one ordered list, Trainer.side_opts.
+own their state (losses.SideOptimizer: Trainer.bil, .pose, .app) and are one
+ordered list, Trainer.side_opts.
 
 model="2dgs" runs examples/simple_trainer_2dgs.py's default step instead:
 rasterization_2dgs(render_mode="RGB+D") (simple_trainer_2dgs.py:549-563), the
@@ -28,11 +29,11 @@ is the colours-only step unchanged (the reference multiplies the terms by 0).
 `bilateral_grid=True` (3DGS, simple_trainer.py `use_bilateral_grid`): the
 render goes through the camera's bilateral grid before the loss
 (bilagrid.bilagrid_slice) and 10 x the grids' total variation is added; the
-grids `bil_grids` [cameras, 12, L, Hg, Wg] have their own FusedAdam, stepped
+grids `bil.grids` [cameras, 12, L, Hg, Wg] have their own FusedAdam, stepped
 densely every step.  evaluate() renders without the grid.
 
 `pose_opt=True` (3DGS, simple_trainer.py `pose_opt`): the camera is adjusted
-by its row of `pose_embeds` [cameras, 9] before the render (pose.pose_apply,
+by its row of `pose.embeds` [cameras, 9] before the render (pose.pose_apply,
 `pose_noise` a fixed perturbation applied first), the projection backward
 that runs the geometry Adam also leaves the pose partials, and
 pose.pose_bwd_adam turns them into the row's gradient and steps the table's
@@ -51,11 +52,11 @@ device index, so the step stays fused and graph-replayed.
 `app_opt=True` (3DGS, simple_trainer.py `app_opt` / `app_embed_dim` /
 `app_opt_lr` / `app_opt_reg`): the colours come from the appearance MLP
 (appearance.py) over the groups `features` [N,32] and `colors` [N,3] (logits),
-which replace sh0 / shN, the step's row of `app_embeds` [cameras, 16] and the
+which replace sh0 / shN, the step's row of `app.embeds` [cameras, 16] and the
 view direction's SH bases at the step's degree; evaluated after the projection
 under its radii mask, the means gradient handed to the geometry Adam as the SH
 backward's is.  One more launch sums the backward's partial sums and steps the
-module's two Adam optimizers (head `app_head`; the table at 10 x the rate with
+module's two Adam optimizers (head `app.head`; the table at 10 x the rate with
 weight decay, densely).  evaluate() renders with the zero embedding.
 
 With `strategy=DefaultStrategyConfig()` the step also runs the reference's
@@ -102,7 +103,7 @@ camera each step:
 import dataclasses
 import math
 import os
-from typing import Callable, Optional, Union
+from typing import Optional, Union
 
 import numpy as np
 import torch
@@ -112,8 +113,11 @@ from . import densify
 from .densify import DefaultStrategyConfig
 from . import mcmc as _mcmc
 from .mcmc import MCMCStrategyConfig
-from .losses import FusedAdam, adam_factors, l1_ssim_loss, ssim_and_l1
+from .losses import FusedAdam, l1_ssim_loss, ssim_and_l1
 from . import _lib, _wrapper
+from .appearance import AppearanceOptimizer
+from .bilagrid import BilateralGridOptimizer
+from .pose import PoseOptimizer
 from .rendering import rasterization, rasterization_2dgs
 from .strategy import activate, update_state_
 
@@ -237,26 +241,7 @@ class StepInputs:
     bkgd: Optional[torch.Tensor] = None  # random_bkgd: the step's colour, device float32 [1,3]
     vote: bool = False  # several ranks: agree on the void flag beside the loss kernels
     capturing: bool = False  # sharded optimizer: collectives in order, no deferred gather
-
-
-@dataclasses.dataclass
-class SideOptimizer:
-    """An Adam beside the Gaussians' (the bilateral grids', the pose table's,
-    the appearance module's), launched after it in Trainer.side_opts' order.
-    `counter`: (object, attribute) of its step count; `factors(it)`: the floats
-    of its slot `name` of the captured step's block for the step after that
-    count; `launch(inputs, hyper)`: with hyper None the host's factors, counting
-    the step itself (as FusedAdam.step does), else the slot's, the count being
-    the caller's business; `workspace`: allocated outside a capture."""
-    name: str
-    counter: tuple
-    factors: Callable
-    launch: Callable
-    workspace: Optional[Callable] = None
-
-    def advance(self, n: int):
-        obj, attr = self.counter
-        setattr(obj, attr, getattr(obj, attr) + n)
+    geom_applied: bool = False  # _run_step sets it: Trainer.geom_applied, for the side launches
 
 
 # Trainer options of the one-GPU dense trainer, and the companions (Trainer.
@@ -310,8 +295,6 @@ def _one_grad(device):
 class Trainer:
     """Holds the Gaussian parameters, Adam state and strategy statistics."""
 
-    BIL_TV_WEIGHT = 10.0  # simple_trainer.py:664: loss += 10 * tv
-
     # every option flag and lazily set attribute has its default here, so a
     # Trainer that did not go through __init__ (a test's skeleton) reads them too
     model = "3dgs"
@@ -325,7 +308,10 @@ class Trainer:
     rasterize_mode = "classic"
     opacity_reg = scale_reg = 0.0
     dp_emulate_world = _sh_pg = None
-    side_opts = ()
+    # the owners of the grids', the pose table's and the appearance module's state
+    # (None: off); `sides`: those that exist; `side_opts`: those optimised, launch order
+    bil = pose = app = None
+    sides = side_opts = ()
     _graph = graph_fallback = None
     _param_gen = 0
     split_div = split_threshold = None
@@ -387,19 +373,14 @@ class Trainer:
         if self.random_bkgd:
             _refuse("random_bkgd", asked)
         # simple_trainer.py app_opt / app_embed_dim / app_opt_lr / app_opt_reg
-        # (:243-254, 389-410): the colours from the appearance MLP over
-        # `features` [N,32], a per-image embedding and the view direction's SH
-        # bases, plus the logits `colors` (appearance.py)
+        # (:243-254, 389-410): the colours from appearance.AppearanceOptimizer
         self.app_opt = bool(app_opt)
         self.app_opt_reg = float(app_opt_reg)
         if self.app_opt:
             _refuse("app_opt", asked)
-            if int(app_embed_dim) != 16:
-                raise ValueError("app_opt: app_embed_dim is fixed at 16 (the kernels' layout), "
-                                 f"got {app_embed_dim!r}")
-            if int(sh_degree) != 3:
-                raise ValueError("app_opt: sh_degree is fixed at 3 (the module's 16 bases), "
-                                 f"got {sh_degree!r}")
+            self.app = AppearanceOptimizer(
+                len(viewmats), rgbs, device, seed, float(app_opt_lr) * math.sqrt(world_size),
+                self.app_opt_reg, app_embed_dim, sh_degree)
         # simple_trainer.py depth_loss / depth_lambda (:163-165, 647-665): the
         # disparity L1 at each image's projected SfM points (depth_loss.py),
         # added to the loss times depth_lambda * scene_scale; the step then
@@ -413,26 +394,28 @@ class Trainer:
             if len(depth_points) != len(viewmats):
                 raise ValueError(f"depth_loss: {len(depth_points)} depth_points entries for "
                                  f"{len(viewmats)} training images")
-        # simple_trainer.py pose_opt / pose_opt_lr / pose_opt_reg / pose_noise:
-        # a pose row per training image refined by its own Adam (pose.py); the
-        # step stays fused: only where the geometry Adam runs in the
-        # projection backward (that backward forms the pose partials)
+        # simple_trainer.py pose_opt / pose_opt_lr / pose_opt_reg / pose_noise
+        # (pose.PoseOptimizer); the step stays fused: only where the geometry Adam
+        # runs in the projection backward (that backward forms the pose partials)
         self.pose_opt, self.pose_noise = bool(pose_opt), float(pose_noise)
         self.pose_opt_reg = float(pose_opt_reg)
         if self.pose_noise < 0.0:
             raise ValueError(f"pose_noise: a standard deviation >= 0, got {pose_noise!r}")
         if self.pose_active:
             _refuse("pose", asked, "pose_opt" if self.pose_opt else "pose_noise")
-        # simple_trainer.py use_bilateral_grid / bilateral_grid_shape: one grid
-        # of affine colour transforms per training image, sliced between the
-        # render and the loss (bilagrid.py)
+            self.pose = PoseOptimizer(
+                len(viewmats), device, seed, self.pose_opt, self.pose_noise,
+                float(pose_opt_lr) * math.sqrt(world_size), self.pose_opt_reg, max_steps)
+        # simple_trainer.py use_bilateral_grid / bilateral_grid_shape: the grids
+        # sliced between the render and the loss (bilagrid.BilateralGridOptimizer)
         self.bilateral_grid = bool(bilateral_grid)
         self.bilateral_grid_shape = tuple(int(v) for v in bilateral_grid_shape)
         if self.bilateral_grid:
             _refuse("bilateral_grid", asked)
-            if len(self.bilateral_grid_shape) != 3 or min(self.bilateral_grid_shape) < 2:
-                raise ValueError("bilateral_grid_shape: (X, Y, W), each >= 2, got "
-                                 f"{bilateral_grid_shape!r}")
+            self.bil = BilateralGridOptimizer(len(viewmats), bilateral_grid_shape, device,
+                                              world_size, max_steps)
+        self.sides = [so for so in (self.bil, self.pose, self.app) if so is not None]
+        self.side_opts = [so for so in self.sides if so.optimised]
         # simple_trainer_2dgs.py:149-160, 611-632: the normal-consistency and
         # depth-distortion terms, each from its start iteration on (step >
         # start_iter)
@@ -488,39 +471,10 @@ class Trainer:
         if self.app_opt:
             # simple_trainer.py:243-254: `features` U(0,1) [N,32] and the logits
             # `colors` replace sh0 / shN, ordinary groups of the trainer's Adam
-            # (refine, relocate, sample-add carry them like any parameter).
-            # Every app_opt draw comes from a generator of its own.  The rgbs
-            # are clamped to [1/512, 1 - 1/512] first: the reference's plain
-            # logit gives +-inf for pure black or white SfM points
-            from . import appearance as _app
-            ga_ = torch.Generator().manual_seed(seed + 2027)
+            # (refine, relocate, sample-add carry them like any parameter),
+            # drawn with the module (AppearanceOptimizer.groups)
             del self.params["sh0"], self.params["shN"]
-            self.params["features"] = torch.rand(N, _app.FEATURE_DIM, generator=ga_)
-            self.params["colors"] = torch.logit(rgbs.float().clamp(1.0 / 512, 1.0 - 1.0 / 512))
-            n_img = len(viewmats)
-            # utils.py AppearanceOptModule: embeds.weight N(0,1) [n_img,16]; the
-            # head's Linear layers at torch's default initialisation
-            # (U(+-1/sqrt(fan_in)) for weights and biases), the last layer zero.
-            # The head is one flat buffer in the order W1, b1, W2, b2, W3, b3
-            app_embeds = torch.randn(n_img, _app.EMBED_DIM, generator=ga_)
-            bound = 1.0 / math.sqrt(_app.WIDTH)
-            flat = (torch.rand(_app.HEAD_NUMEL, generator=ga_) * 2.0 - 1.0) * bound
-            flat[2 * (_app.WIDTH * _app.WIDTH + _app.WIDTH):] = 0.0
-            self.app_embeds = app_embeds.to(device)
-            self._app_flat = flat.to(device)
-            self.app_head, o_ = [], 0
-            for shape in _app.HEAD_SHAPES:
-                n_ = int(np.prod(shape))
-                self.app_head.append(self._app_flat[o_:o_ + n_].view(shape))
-                o_ += n_
-            self._app_head_m = torch.zeros(_app.HEAD_NUMEL, device=device)
-            self._app_head_v = torch.zeros(_app.HEAD_NUMEL, device=device)
-            self._app_embed_m = torch.zeros(n_img, _app.EMBED_DIM, device=device)
-            self._app_embed_v = torch.zeros(n_img, _app.EMBED_DIM, device=device)
-            self._app_grads = torch.zeros(_app.HEAD_NUMEL + _app.EMBED_DIM, device=device)
-            self._app_ws = None
-            self.app_step_count = 0
-            self.app_lr = float(app_opt_lr) * math.sqrt(world_size)
+            self.params.update(self.app.__dict__.pop("groups"))
         # Gaussian-sharded: this rank's Gaussians [rank::world] of the scene
         # initialised as a whole (simple_trainer.py:221-229: knn scales over
         # all points, then the slice), so the shards together are the
@@ -611,35 +565,8 @@ class Trainer:
         self._sh_ready = 0
         self.opt = self._make_optimizer(list(self.params.values()))
         self._register_hooks()
-        if self.bilateral_grid:
-            # simple_trainer.py:300-318: Adam(lr 2e-3 sqrt(BS), eps 1e-15) on the
-            # grids, stepped densely over all images every step, its lr on the
-            # chained warm-up / decay schedule (bilagrid_lr)
-            from .bilagrid import bilagrid_identity
-            self.bil_grids = torch.nn.Parameter(
-                bilagrid_identity(len(viewmats), self.bilateral_grid_shape, device=device))
-            self.bil_lr = 2e-3 * math.sqrt(BS)
-            self.bil_opt = FusedAdam([self.bil_grids], [self.bil_lr], betas=(0.9, 0.999),
-                                     eps=1e-15)
-        self.pose_lr = float(pose_opt_lr) * math.sqrt(BS)
-        if self.pose_active:
-            assert self.geom_in_proj, "pose_opt: the geometry Adam in the projection backward"
-            n_img = len(viewmats)
-            # utils.py CameraOptModule: embeds.weight [n, 9], zero_init; its
-            # Adam(lr pose_opt_lr sqrt(BS), weight_decay pose_opt_reg) state
-            self.pose_embeds = torch.zeros(n_img, 9, device=device)
-            self._pose_m = torch.zeros(n_img, 9, device=device)
-            self._pose_v = torch.zeros(n_img, 9, device=device)
-            self.pose_step_count = 0
-            # pose_perturb.random_init(pose_noise): a fixed table N(0, pose_noise)
-            # from a generator of its own (the Gaussians' draws are a plain trainer's)
-            self.pose_noise_table = None
-            if self.pose_noise > 0.0:
-                gp = torch.Generator().manual_seed(seed + 1013)
-                self.pose_noise_table = (torch.randn(n_img, 9, generator=gp)
-                                         * self.pose_noise).to(device)
-            self._pose_vm = torch.empty(1, 4, 4, device=device)  # the step's view matrix
-            self._pose_ws = None
+        assert self.pose is None or self.geom_in_proj, \
+            "pose_opt: the geometry Adam in the projection backward"
         if self.depth_loss:
             # the images' points as CSR tables on the device, built once; the
             # step names its image by a device index
@@ -648,7 +575,6 @@ class Trainer:
         # an eager step names its image by a one-element view of this table (the
         # captured step: by the camera index of its input block)
         self._cam_index = torch.arange(len(viewmats), dtype=torch.int64, device=device)
-        self.side_opts = self._side_optimizers()
         self.viewmats = viewmats.to(device)
         self.Ks = Ks.to(device)
         if targets is None:
@@ -730,134 +656,30 @@ class Trainer:
 
     def moments(self):
         """name -> [exp_avg, exp_avg_sq] as full tensors shaped like the
-        parameter (gathered over the ranks for the sharded optimizer); with
-        the bilateral grid, "bil_grids" holds the grid optimizer's."""
+        parameter (gathered over the ranks for the sharded optimizer), then the
+        side optimizers' ("bil_grids", "pose_embeds", "app_embeds", "app_head")."""
         out = self._gaussian_moments()
-        if self.bilateral_grid:
-            out["bil_grids"] = [self.bil_opt.exp_avg[0], self.bil_opt.exp_avg_sq[0]]
-        if self.pose_opt:
+        if self.side_opts:
             self.sync()
-            out["pose_embeds"] = [self._pose_m, self._pose_v]
-        if self.app_opt:
-            self.sync()
-            out["app_embeds"] = [self._app_embed_m, self._app_embed_v]
-            out["app_head"] = [self._app_head_m, self._app_head_v]  # flat, W1 b1 W2 b2 W3 b3
+        for so in self.side_opts:
+            out.update(so.moments())
         return out
 
-    # ------------------------------------------------------------- app_opt
+    # --------------------------------------------- pose_opt, app_opt: access
     def app_state_dict(self):
         """The appearance module's state under the reference module's keys
-        (utils.py AppearanceOptModule: `embeds.weight`,
-        `color_head.{0,2,4}.{weight,bias}`), so checkpoints interchange."""
-        from .appearance import HEAD_KEYS
+        (AppearanceOptimizer.state_dict), synced."""
         self.sync()
-        out = {"embeds.weight": self.app_embeds.detach().clone()}
-        for k, t in zip(HEAD_KEYS, self.app_head):
-            out[k] = t.detach().clone()
-        return out
+        return self.app.state_dict()
 
-    def _app_colors(self, viewmats, sh_degree, cam_index, fusion):
-        """rasterization(_app=...)'s callable: the colours [1,N,3] of the camera
-        `viewmats` [1,4,4] from the projection's radii (invisible Gaussians are
-        skipped), the embedding row of the device index `cam_index` (None: the
-        zero embedding of the reference's evaluation)."""
-        from .appearance import trainer_colors
-        p = self.params
-        self._app_workspace()
-        vm = viewmats.detach()
-        # the camera centre -R^T t, elementwise on the device
-        campos = -(vm[:, :3, :3] * vm[:, :3, 3:4]).sum(1)
-        return lambda radii: trainer_colors(
-            p["features"], p["colors"], p["means"], radii, campos, self.app_head, sh_degree,
-            None if cam_index is None else self.app_embeds, cam_index, self._app_ws, fusion)
-
-    def _app_workspace(self):
-        """The colour backward's partial sums, sized for the Gaussians."""
-        n = self.params["means"].shape[0]
-        if self._app_ws is None or self._app_ws_n != n:
-            from .appearance import app_workspace
-            self._app_ws, self._app_ws_n = app_workspace(n, 1, self.device), n
-        return self._app_ws
-
-    def _app_launch(self, s: StepInputs, hyper):
-        """After the backward: the ordered sum of the colour backward's partial
-        sums and the module's two Adam optimizers in place (head: lr; the
-        embedding table: 10 x lr with app_opt_reg as weight decay, dense)."""
-        from .appearance import app_reduce_adam
-        if hyper is None:
-            self.app_step_count += 1
-        app_reduce_adam(self._app_ws, self.params["means"].shape[0], 1, self._app_grads,
-                        self.app_head, self._app_head_m, self._app_head_v, self.app_lr,
-                        self.app_step_count, embeds=self.app_embeds,
-                        embed_ids=s.cam, embed_exp_avg=self._app_embed_m,
-                        embed_exp_avg_sq=self._app_embed_v,
-                        embed_weight_decay=self.app_opt_reg, hyper=hyper, skip=s.void)
-
-    def _app_factors(self, it: int):
-        """torch's Adam for the head (lr) and the embedding table (10 x lr)."""
-        from .appearance import BETAS, EMBED_LR_MULT
-        (sh, ib), (se, _) = adam_factors([self.app_lr, self.app_lr * EMBED_LR_MULT], BETAS,
-                                         self.app_step_count + 1)
-        return sh, ib, se, 0.0
-
-    # ----------------------------------------------------- side optimizers
-    def _side_optimizers(self):
-        """The Adam launches after the Gaussians', in launch order: the
-        bilateral grids', the pose table's, the appearance module's."""
-        out = []
-        if self.bilateral_grid:
-            out.append(SideOptimizer("bil", (self.bil_opt, "step_count"), self._bil_factors,
-                                     self._bil_launch))
-        if self.pose_opt:
-            out.append(SideOptimizer("pose", (self, "pose_step_count"), self._pose_factors,
-                                     self._pose_launch, self._pose_workspace))
-        if self.app_opt:
-            out.append(SideOptimizer("app", (self, "app_step_count"), self._app_factors,
-                                     self._app_launch, self._app_workspace))
-        return out
-
-    def _bil_factors(self, it: int):
-        """The grids' Adam: its own betas, the chained schedule's lr."""
-        from .bilagrid import bilagrid_lr
-        bo = self.bil_opt
-        bo.lrs[0] = bilagrid_lr(it, self.max_steps, self.bil_lr)
-        return adam_factors(bo.lrs, bo.betas, bo.step_count + 1)[0]
-
-    def _bil_launch(self, s: StepInputs, hyper):
-        """simple_trainer.py:300-318: the grids' Adam, densely over all images."""
-        if hyper is None:
-            self._bil_factors(s.it)  # (sets this step's learning rate)
-            self.bil_opt.step()
-        else:
-            self.bil_opt.step(hyper=hyper, void=s.void)
-        self.bil_opt.zero_grad()
-
-    # ----------------------------------------------------------- pose_opt
     @property
     def pose_active(self) -> bool:
         """The step renders through pose.pose_apply (pose_opt or pose_noise)."""
         return self.pose_opt or self.pose_noise > 0.0
 
     def pose_lr_at(self, it: int) -> float:
-        """The pose optimizer's learning rate at step `it`: pose_opt_lr sqrt(BS),
-        on ExponentialLR(0.01 ** (1 / max_steps)) when max_steps is set."""
-        from .pose import pose_lr
-        return pose_lr(it, self.max_steps, self.pose_lr)
-
-    def _pose_workspace(self):
-        """The projection backward's pose partials, sized for the Gaussians."""
-        from .pose import pose_workspace
-        n = self.params["means"].shape[0]
-        if self._pose_ws is None or self._pose_ws.numel() < 16 * ((n + 255) // 256):
-            self._pose_ws = pose_workspace(n, self.device)
-        return self._pose_ws
-
-    def _pose_viewmat(self, base, cam_index, out=None):
-        """Launch (a): `base` [1,4,4] adjusted by the noise and embedding rows of
-        the device index `cam_index` into `out` (default: the step's buffer)."""
-        from .pose import pose_apply
-        return pose_apply(base, cam_index, self.pose_embeds if self.pose_opt else None,
-                          self.pose_noise_table, out=self._pose_vm if out is None else out)
+        """The pose optimizer's learning rate at step `it` (PoseOptimizer.lr_at)."""
+        return self.pose.lr_at(it)
 
     @torch.no_grad()
     def adjusted_viewmats(self, ids=None):
@@ -866,32 +688,12 @@ class Trainer:
         self.sync()
         ids = list(range(len(self.viewmats))) if ids is None else [int(i) for i in ids]
         vms = self.viewmats.float().contiguous()
-        if not self.pose_active:
+        if self.pose is None:
             return vms[ids].clone()
         out = torch.empty(len(ids), 4, 4, device=vms.device)
         for k, ci in enumerate(ids):
-            self._pose_viewmat(vms[ci:ci + 1], self._cam_index[ci:ci + 1], out=out[k:k + 1])
+            self.pose.apply(vms[ci:ci + 1], self._cam_index[ci:ci + 1], out=out[k:k + 1])
         return out
-
-    def _pose_factors(self, it: int):
-        from .pose import BETAS
-        return adam_factors([self.pose_lr_at(it)], BETAS, self.pose_step_count + 1)[0]
-
-    def _pose_launch(self, s: StepInputs, hyper):
-        """Launch (c): the pose gradient from the projection backward's partials
-        and the pose Adam over the whole table."""
-        from .pose import pose_bwd_adam
-        if not self.geom_applied:
-            raise RuntimeError("pose_opt: the projection backward did not run the geometry "
-                               "Adam, so it formed no pose gradient (a loss term outside the "
-                               "render reached the geometry parameters?)")
-        lr, step = 0.0, 1  # unused with the device factors
-        if hyper is None:
-            self.pose_step_count += 1
-            lr, step = self.pose_lr_at(s.it), self.pose_step_count
-        pose_bwd_adam(self._pose_ws, self.params["means"].shape[0], _wrapper._f32c(s.viewmats),
-                      s.cam, self.pose_embeds, self._pose_m, self._pose_v, lr, self.pose_opt_reg,
-                      step, noise=self.pose_noise_table, hyper=hyper, skip=s.void)
 
     def _gaussian_moments(self):
         names = list(self.params)
@@ -913,10 +715,8 @@ class Trainer:
     def _load_moments(self, moments):
         params = list(self.params.values())
         names = list(self.params)
-        if "bil_grids" in moments and self.bilateral_grid:
-            self.bil_opt.params = [self.bil_grids]
-            self.bil_opt.exp_avg = [moments["bil_grids"][0]]
-            self.bil_opt.exp_avg_sq = [moments["bil_grids"][1]]
+        for so in self.side_opts:  # (those that `moments` names: a checkpoint's)
+            so.load_moments(moments)
         if self.sharded:
             step = self.opt.step_count
             self.opt = self._make_optimizer(params)
@@ -1056,8 +856,8 @@ class Trainer:
         else:  # this rank's camera of the step's
             r = self.rank if self.gshard else 0
             vms, K = viewmats[r:r + 1], Ks[r:r + 1]
-        if cam_index is not None and self.pose_active:  # launch (a): the step's view matrix
-            vms = self._pose_viewmat(_wrapper._f32c(vms), cam_index)
+        if cam_index is not None and self.pose is not None:  # launch (a): the step's view matrix
+            vms = self.pose.apply(_wrapper._f32c(vms), cam_index)
         absgrad = getattr(self.strategy, "absgrad", False)
         if self.model == "2dgs":
             if hook is not None:
@@ -1085,7 +885,7 @@ class Trainer:
             # the colours of the appearance MLP at `deg`, rendered as plain
             # colours (sh_degree None), evaluated after the projection
             coeffs, deg_r = p["colors"], None
-            dkw["_app"] = self._app_colors(vms, deg, cam_index, fusion)
+            dkw["_app"] = self.app.colors(p, vms, deg, cam_index, fusion)
         else:
             coeffs, deg_r = ((p["sh0"], p["shN"]) if self.fused
                              else torch.cat([p["sh0"], p["shN"]], 1)), deg
@@ -1110,9 +910,7 @@ class Trainer:
         from . import depth_loss as _dl
         weight = self.depth_lambda * self.scene_scale
         if self.bilateral_grid:
-            from .bilagrid import _slice_tv
-            colors, tv = _slice_tv(self.bil_grids, _dl.colour_channels(rgbd), cam_index,
-                                   self.BIL_TV_WEIGHT)
+            colors, tv = self.bil.slice_tv(_dl.colour_channels(rgbd), cam_index)
             photo = l1_ssim_loss(colors, gt, self.ssim_lambda, gt_index=gt_index)
             term = _dl.table_depth_loss(rgbd, alphas, self.depth_table, cam_index, 3)
             return photo, weight * term, tv
@@ -1267,8 +1065,7 @@ class Trainer:
         if self.bilateral_grid and not self.depth_loss:
             # simple_trainer.py:620-630, 663-665: the camera's grid applied to
             # the render, 10 x the grids' total variation added to the loss
-            from .bilagrid import _slice_tv
-            colors, tv = _slice_tv(self.bil_grids, colors, s.cam, self.BIL_TV_WEIGHT)
+            colors, tv = self.bil.slice_tv(colors, s.cam)
         vote = None
         if s.vote:  # the ranks' overflow flags, agreed beside the loss kernels
             import torch.distributed as dist
@@ -1323,8 +1120,8 @@ class Trainer:
         if s.stats:
             self.update_state(meta, skip=s.void)
         # whether this step's geometry update ran inside the projection backward
-        self.geom_applied = bool(fusion is not None and fusion.geom_adam is not None
-                                 and fusion.geom_adam.applied)
+        s.geom_applied = self.geom_applied = bool(
+            fusion is not None and fusion.geom_adam is not None and fusion.geom_adam.applied)
         xform = self._geom_xform(fusion)
         hyper = s.hyper
         if self.sharded:  # reduce-scatter, Adam on this rank's rows, all-gather
@@ -1413,7 +1210,7 @@ class Trainer:
                 hyper = s.hyper[:2 * len(idx)]
             ga = self.geom_adam_in_backward(step, hyper=hyper, skip=s.void)
             if self.pose_opt:
-                ga.pose_ws = self._pose_workspace()
+                ga.pose_ws = self.pose.prepare(self.params["means"].shape[0])
         if fa is None and not geom:
             return None
         return _wrapper.StepFusion(sh_adam=fa, geom=geom, geom_adam=ga)
@@ -1552,9 +1349,9 @@ class Trainer:
         os.makedirs(compress_dir, exist_ok=True)
         comp.compress(compress_dir, {k: p.data for k, p in self.synced_params().items()})
         splats = comp.decompress(compress_dir)
-        # the appearance workspace is sized for the Gaussians (a captured step
+        # a side optimizer's workspace is sized for the Gaussians (a captured step
         # holds its address): the renders of the n^2 get one of their own
-        keep = {k: self.__dict__[k] for k in ("_app_ws", "_app_ws_n") if k in self.__dict__}
+        keep = [(so, so.ws, so.ws_n) for so in self.side_opts]
         saved = self.params
         try:
             self.params = {k: splats[k].to(self.device, saved[k].dtype).contiguous()
@@ -1563,7 +1360,8 @@ class Trainer:
             out["num_GS"] = int(self.params["means"].shape[0])
         finally:
             self.params = saved
-            self.__dict__.update(keep)
+            for so, ws, n in keep:
+                so.ws, so.ws_n = ws, n
         out["compressed_bytes"] = sum(
             os.path.getsize(os.path.join(compress_dir, f)) for f in os.listdir(compress_dir)
             if os.path.isfile(os.path.join(compress_dir, f)))

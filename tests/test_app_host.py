@@ -176,22 +176,22 @@ def test_trainer_state(init):
         assert torch.equal(tr.params[k], plain.params[k]), k
     assert list(off.params) == list(plain.params)
     assert all(torch.equal(off.params[k], plain.params[k]) for k in plain.params)
-    assert not hasattr(plain, "app_embeds")
+    assert plain.app is None
     # the module: N(0,1) table, Linear default init, zero last layer
-    assert tr.app_embeds.shape == (3, 16) and float(tr.app_embeds.std()) > 0.5
-    assert [tuple(t.shape) for t in tr.app_head] == list(HEAD_SHAPES)
+    assert tr.app.embeds.shape == (3, 16) and float(tr.app.embeds.std()) > 0.5
+    assert [tuple(t.shape) for t in tr.app.head] == list(HEAD_SHAPES)
     bound = 1.0 / 8.0
-    for t in tr.app_head[:4]:
+    for t in tr.app.head[:4]:
         assert float(t.abs().max()) <= bound and float(t.abs().max()) > 0.5 * bound
-    assert not tr.app_head[4].any() and not tr.app_head[5].any()
+    assert not tr.app.head[4].any() and not tr.app.head[5].any()
     sd = tr.app_state_dict()
     assert set(sd) == {"embeds.weight"} | set(HEAD_KEYS)
-    assert torch.equal(sd["embeds.weight"], tr.app_embeds)
-    for k, t in zip(HEAD_KEYS, tr.app_head):
+    assert torch.equal(sd["embeds.weight"], tr.app.embeds)
+    for k, t in zip(HEAD_KEYS, tr.app.head):
         assert torch.equal(sd[k], t)
     # ordinary optimizer groups with the reference's learning rates
     assert tr.lrs[4] == tr.lrs[5] == 2.5e-3
-    assert tr.app_lr == 1e-3 and tr.app_opt_reg == 1e-6
+    assert tr.app.lr == 1e-3 and tr.app_opt_reg == 1e-6
     assert not tr.sh_adam_in_bwd
     moms = tr.moments()
     assert set(moms) == set(tr.params) | {"app_embeds", "app_head"}

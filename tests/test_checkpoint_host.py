@@ -120,7 +120,7 @@ def test_round_trip_restores_a_trainer_of_another_seed(tmp_path):
     assert torch.equal(a.grad2d, b.grad2d) and torch.equal(a.count, b.count)
     assert b.refine_log == [(5, 1, 2, N)] and b._noise_seed == a._noise_seed
     assert torch.equal(a.rng.get_state(), b.rng.get_state())
-    assert torch.equal(a.pose_noise_table, b.pose_noise_table)
+    assert torch.equal(a.pose.noise, b.pose.noise)
     assert (b.split_div, b.split_threshold, b.split_launch, b._split_tuned) == (1100, 640, 1, True)
     # the saving trainer is untouched
     assert a.opt.step_count == 11 and a._param_gen == 0
@@ -193,3 +193,96 @@ def test_torch_optimizers_round_trip(tmp_path, kw):
         assert torch.equal(st["exp_avg_sq"], a.moments()[k][1])
         assert torch.equal(p, a.params[k])
     assert [g_["params"][0] for g_ in b.opt.param_groups] == list(b.params.values())
+
+
+# ---- files written before the side optimizers owned their state
+# (tests/golden/make_golden_checkpoint.py: 8 Gaussians, 3 images of 16 x 16)
+GOLDEN = ("app", "pose")
+
+
+def golden_trainer(name, seed):
+    from gsplat_hip.densify import DefaultStrategyConfig
+    from gsplat_hip.train_step import Trainer
+    kw = {"pose": dict(pose_opt=True, pose_noise=0.01, strategy=DefaultStrategyConfig()),
+          "app": dict(app_opt=True)}[name]
+    g = torch.Generator().manual_seed(1)
+    return Trainer(torch.randn(8, 3, generator=g), torch.rand(8, 3, generator=g),
+                   torch.eye(4)[None].repeat(N_IMG, 1, 1), torch.eye(3)[None].repeat(N_IMG, 1, 1),
+                   16, 16, device="cpu", seed=seed, bilateral_grid=True,
+                   bilateral_grid_shape=(2, 2, 2), **kw)
+
+
+def golden_file(name):
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                        f"checkpoint_{name}.pt")
+    return path, torch.load(path, map_location="cpu", weights_only=True)
+
+
+def assert_same(a, b, where="checkpoint"):
+    """torch.equal on every tensor, == on everything else, the same keys."""
+    assert type(a) is type(b), where
+    if isinstance(a, dict):
+        assert set(a) == set(b), (where, sorted(a), sorted(b))
+        for k in a:
+            assert_same(a[k], b[k], f"{where}[{k!r}]")
+    elif isinstance(a, list):
+        assert len(a) == len(b), where
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert_same(x, y, f"{where}[{i}]")
+    elif torch.is_tensor(a):
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), where
+    else:
+        assert a == b, (where, a, b)
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN))
+def test_constructor_draws_match_the_golden_files(name):
+    """A fresh trainer with the file's seed holds what the constructor of the
+    trainer that wrote the file produced."""
+    _, ck = golden_file(name)
+    fresh = ck["fresh"]
+    tr = golden_trainer(name, fresh["seed"])
+    assert_same({k: p.detach() for k, p in tr.params.items()}, fresh["params"], "params")
+    if name == "pose":
+        assert torch.equal(tr.pose.noise, fresh["pose_noise"])
+        assert not tr.pose.embeds.any() and tr.pose.step_count == 0
+    else:
+        assert torch.equal(tr.app.embeds, fresh["app_embeds"])
+        assert_same([t for t in tr.app.head], fresh["app_head"], "app_head")
+    assert tr.bil.opt.step_count == 0
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN))
+def test_golden_file_resumes_into_the_same_state(name):
+    """load_checkpoint of a file of the earlier layout of the trainer's state,
+    then checkpoint.state: the file's dictionary, tensor for tensor."""
+    from gsplat_hip import checkpoint
+    path, ck = golden_file(name)
+    seed = ck.pop("fresh")["seed"]
+    tr = golden_trainer(name, seed + 1)
+    assert tr.load_checkpoint(path) == ck["step"]
+    assert_same(checkpoint.state(tr, ck["step"]), ck)
+    assert ck["gsplat_hip"]["side_steps"] == {"pose": {"bil": 11, "pose": 9},
+                                              "app": {"bil": 11, "app": 7}}[name]
+
+
+def test_golden_pose_file_on_the_evaluation_path():
+    """resume=False: the pose table copied, its moments and step count zero;
+    the grids, their moments and step count, and the noise table kept."""
+    path, ck = golden_file("pose")
+    tr = golden_trainer("pose", ck["fresh"]["seed"] + 1)
+    tr.pose.step_count, tr.bil.opt.step_count = 4, 5
+    for t in tr.pose.moments()["pose_embeds"] + tr.bil.moments()["bil_grids"]:
+        t.fill_(0.5)
+    with torch.no_grad():
+        tr.bil.grids.mul_(2.0)
+    grids, noise = tr.bil.grids.detach().clone(), tr.pose.noise.clone()
+    assert tr.load_checkpoint(path, resume=False) == ck["step"]
+    assert_same({k: p.detach() for k, p in tr.params.items()}, ck["splats"], "splats")
+    assert torch.equal(tr.pose.embeds, ck["pose_adjust"]["embeds.weight"])
+    assert tr.pose.step_count == 0 and tr.opt.step_count == 0
+    assert all(not t.any() for t in tr.moments()["pose_embeds"])
+    assert tr.bil.opt.step_count == 5 and torch.equal(tr.bil.grids, grids)
+    assert all(bool((t == 0.5).all()) for t in tr.moments()["bil_grids"])
+    assert torch.equal(tr.pose.noise, noise)

@@ -101,20 +101,20 @@ def tensors(tr):
     if tr.radii2d is not None:
         out["radii2d"] = tr.radii2d
     if tr.bilateral_grid:
-        out["bil_grids"] = tr.bil_grids.detach()
+        out["bil_grids"] = tr.bil.grids.detach()
     if tr.pose_opt:
-        out["pose_embeds"] = tr.pose_embeds
-    if tr.pose_active and tr.pose_noise_table is not None:
-        out["pose_noise_table"] = tr.pose_noise_table
+        out["pose_embeds"] = tr.pose.embeds
+    if tr.pose_active and tr.pose.noise is not None:
+        out["pose_noise_table"] = tr.pose.noise
     if tr.app_opt:
-        out["app_embeds"], out["app_head"] = tr.app_embeds, tr._app_flat
+        out["app_embeds"], out["app_head"] = tr.app.embeds, tr.app.flat
     return {k: v.detach().clone() for k, v in out.items()}
 
 
 def scalars(tr):
     tr.sync()
     return {"adam_step": tr.opt.step_count,
-            "side_steps": {so.name: getattr(*so.counter) for so in tr.side_opts},
+            "side_steps": {so.name: so.step_count for so in tr.side_opts},
             "refine_log": [tuple(r) for r in tr.refine_log],
             "rng": tr.rng.get_state().clone(), "noise_seed": tr._noise_seed,
             "split": (tr.split_div, tr.split_threshold, getattr(tr, "split_launch", None),
@@ -282,7 +282,7 @@ def test_save_ply_bakes_the_appearance(tmp_path):
         tr.step(it)
     C0 = 0.2820947917738781
     p = {k: v.detach().cpu() for k, v in tr.synced_params().items()}
-    head = [t.detach().cpu() for t in tr.app_head]
+    head = [t.detach().cpu() for t in tr.app.head]
     for deg in (None, 1):
         path = str(tmp_path / f"app_{deg}.ply")
         assert tr.save_ply(path, sh_degree=deg) == N

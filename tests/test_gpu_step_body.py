@@ -128,12 +128,12 @@ def _side_state(tr):
     moms = tr.moments()
     out = {}
     if tr.bilateral_grid:
-        out["bil_grids"] = tr.bil_grids.detach()
+        out["bil_grids"] = tr.bil.grids.detach()
     if tr.pose_opt:
-        out["pose_embeds"] = tr.pose_embeds
+        out["pose_embeds"] = tr.pose.embeds
     if tr.app_opt:
-        out["app_embeds"] = tr.app_embeds
-        out["app_head"] = torch.cat([t.reshape(-1) for t in tr.app_head])
+        out["app_embeds"] = tr.app.embeds
+        out["app_head"] = torch.cat([t.reshape(-1) for t in tr.app.head])
     for k in list(out):
         out[k + ".m"], out[k + ".v"] = moms[k][0].reshape(-1), moms[k][1].reshape(-1)
     return {k: v.detach().clone() for k, v in out.items()}
@@ -171,11 +171,11 @@ def test_recovery_with_side_optimizers(name):
     assert g.recaptures >= 2
     for t in (tr_a, tr):
         assert t.opt.step_count == steps
-        assert t.bil_opt.step_count == steps
+        assert t.bil.opt.step_count == steps
         if t.pose_opt:
-            assert t.pose_step_count == steps
+            assert t.pose.step_count == steps
         if t.app_opt:
-            assert t.app_step_count == steps
+            assert t.app.step_count == steps
     assert set(a) == set(b) and len(a) >= 7
     for k in a:
         spread = float((a2[k] - a[k]).abs().max())

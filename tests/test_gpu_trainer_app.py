@@ -53,8 +53,8 @@ def _prepare(tr):
     tr.adam_kw = dict(tr.adam_kw, eps=1e-8)
     if getattr(tr, "app_opt", False):
         g = torch.Generator().manual_seed(5)
-        tr.app_head[4].copy_((torch.randn(3, 64, generator=g) * 0.3).to(DEV))
-        tr.app_head[5].copy_((torch.randn(3, generator=g) * 0.1).to(DEV))
+        tr.app.head[4].copy_((torch.randn(3, 64, generator=g) * 0.3).to(DEV))
+        tr.app.head[5].copy_((torch.randn(3, generator=g) * 0.1).to(DEV))
     return tr
 
 
@@ -68,8 +68,8 @@ def _make(graph=False, **kw):
 def _module_state(tr):
     tr.sync()
     m = tr.moments()
-    return dict(embeds=tr.app_embeds.detach().clone(),
-                head=torch.cat([t.detach().reshape(-1) for t in tr.app_head]).clone(),
+    return dict(embeds=tr.app.embeds.detach().clone(),
+                head=torch.cat([t.detach().reshape(-1) for t in tr.app.head]).clone(),
                 embeds_m=m["app_embeds"][0].clone(), head_m=m["app_head"][0].clone())
 
 
@@ -80,13 +80,13 @@ def test_eager_steps_match_the_torch_composition():
     tr = _make()
     assert tr._graph is None
     p = {k: v.detach().clone().requires_grad_(True) for k, v in tr.params.items()}
-    embeds = tr.app_embeds.detach().clone().requires_grad_(True)
-    head = [t.detach().clone().requires_grad_(True) for t in tr.app_head]
+    embeds = tr.app.embeds.detach().clone().requires_grad_(True)
+    head = [t.detach().clone().requires_grad_(True) for t in tr.app.head]
     opt = FusedAdam(list(p.values()), tr.lrs, **tr.adam_kw)
     opt_head = torch.optim.Adam(head, lr=1e-3)
     opt_embeds = torch.optim.Adam([embeds], lr=1e-3 * 10.0, weight_decay=1e-6)
     want_losses, got_losses = [], []
-    embeds0 = tr.app_embeds.detach().clone()
+    embeds0 = tr.app.embeds.detach().clone()
     for it in range(steps):
         ci = tr.camera_index(it)
         vm = tr.viewmats[ci:ci + 1]
@@ -129,7 +129,7 @@ def test_eager_steps_match_the_torch_composition():
                   f"{err:.3e}")
             assert part > 0.0 and err < 0.5 * part, (part, err)
     tr.sync()
-    assert tr.app_step_count == steps and tr.opt.step_count == steps
+    assert tr.app.step_count == steps and tr.opt.step_count == steps
     print("losses:", got_losses, want_losses)
     torch.testing.assert_close(torch.tensor(got_losses), torch.tensor(want_losses),
                                rtol=1e-4, atol=1e-6)
@@ -179,7 +179,7 @@ def test_graph_trainer_tracks_eager():
     g = b["tr"]._graph
     assert g.replays >= 8 and g.recaptures >= 4
     assert set(g.census) <= {"kernel", "empty"}, g.census
-    assert a["tr"].app_step_count == b["tr"].app_step_count == 8
+    assert a["tr"].app.step_count == b["tr"].app.step_count == 8
     torch.testing.assert_close(b["losses"], a["losses"], rtol=1e-4, atol=1e-6)
     assert len(set(b["losses"].tolist())) == 8
     for k in a["params"]:
@@ -241,7 +241,7 @@ def test_refine_boundary(strategy):
         assert moms[k][0].shape == tr.params[k].shape == moms[k][1].shape
         assert torch.isfinite(tr.params[k]).all()
     assert torch.isfinite(out["losses"]).all() and torch.isfinite(out["params"]["means"]).all()
-    assert tr.app_step_count == 8
+    assert tr.app.step_count == 8
     tr.release_graph()
 
 
@@ -257,7 +257,7 @@ def test_with_bilateral_grid_and_depth_loss():
         torch.testing.assert_close(b["params"][k], a["params"][k], rtol=1e-3, atol=1e-5)
     for k in ("embeds", "head"):
         torch.testing.assert_close(b["module"][k], a["module"][k], rtol=1e-3, atol=1e-5)
-    assert a["tr"].bil_opt.step_count == b["tr"].bil_opt.step_count == 6
+    assert a["tr"].bil.opt.step_count == b["tr"].bil.opt.step_count == 6
     b["tr"].release_graph()
 
 
@@ -274,9 +274,9 @@ def test_evaluate_renders_with_the_zero_embedding():
         vm = tr.viewmats[ci:ci + 1]
         campos = torch.inverse(vm)[:, :3, 3]
         renders = []
-        for e in (torch.zeros(1, 16, device=DEV), tr.app_embeds[ci:ci + 1]):
+        for e in (torch.zeros(1, 16, device=DEV), tr.app.embeds[ci:ci + 1]):
             colors = O.app_colors(p["features"], p["colors"], e, p["means"], campos,
-                                  [t.detach() for t in tr.app_head], 3)
+                                  [t.detach() for t in tr.app.head], 3)
             renders.append(rasterization(
                 p["means"], p["quats"], torch.exp(p["scales"]), torch.sigmoid(p["opacities"]),
                 colors, vm, tr.Ks[ci:ci + 1], tr.width, tr.height, sh_degree=None, packed=False,

@@ -44,7 +44,7 @@ def _trainer_scene(n_cams=4, W=96, H=64, stride=32):
 def _perturb(tr, amount=0.05):
     """Move the grids off the identity, identically for every trainer."""
     g = torch.Generator().manual_seed(11)
-    tr.bil_grids.data.add_((amount * torch.randn(tr.bil_grids.shape, generator=g)).to(DEV))
+    tr.bil.grids.data.add_((amount * torch.randn(tr.bil.grids.shape, generator=g)).to(DEV))
 
 
 def test_eager_step_matches_autograd_of_the_composition():
@@ -53,15 +53,15 @@ def test_eager_step_matches_autograd_of_the_composition():
     means, rgbs, vm, K, W, H = _trainer_scene()
     it = 1
     tr = Trainer(means, rgbs, vm, K, W, H, device=DEV, bilateral_grid=True, max_steps=100)
-    assert tr.bil_grids.shape == (4, 12, 8, 16, 16)
+    assert tr.bil.grids.shape == (4, 12, 8, 16, 16)
     _perturb(tr)
-    grids0 = tr.bil_grids.detach().clone()
+    grids0 = tr.bil.grids.detach().clone()
     ci = tr.camera_index(it)
     with torch.no_grad():  # the step's render (evaluate()'s: without the grid)
         colors = tr.render(ci, tr.sh_degree_at(it))[0].clone()
     loss = float(tr.step(it).detach())
     tr.sync()
-    assert tr.bil_opt.step_count == 1
+    assert tr.bil.opt.step_count == 1
 
     def compose(dtype, dev):
         g = grids0.to(dev, dtype).requires_grad_(True)
@@ -90,10 +90,10 @@ def test_eager_step_matches_autograd_of_the_composition():
     assert err_m <= 0.1 * bar, (err_m, bar)
     assert err_v <= 0.001 * 2.0 * top * bar, (err_v, top, bar)
     # the grids moved, the moments survive a reload (checkpoint / refine path)
-    assert float((tr.bil_grids.detach() - grids0).abs().max()) > 0
+    assert float((tr.bil.grids.detach() - grids0).abs().max()) > 0
     moms = tr.moments()
     tr._load_moments(moms)
-    assert tr.bil_opt.exp_avg[0] is moms["bil_grids"][0]
+    assert tr.bil.opt.exp_avg[0] is moms["bil_grids"][0]
     assert set(moms) == set(tr.params) | {"bil_grids"}
 
 
@@ -131,15 +131,15 @@ def test_graph_trainer_tracks_eager():
                      bilateral_grid=True)
         assert (tr._graph is not None) == graph
         _perturb(tr)
-        start = tr.bil_grids.detach().clone()
+        start = tr.bil.grids.detach().clone()
         losses = [tr.step(it) for it in range(8)]
         tr.sync()
         assert tr.graph_fallback is None, tr.graph_fallback
         assert sorted({tr.camera_index(it) for it in range(8)}) == [0, 1, 2, 3]
         out[run] = ({k: p.detach().clone() for k, p in tr.params.items()},
                     [m.clone() for m in tr.opt.exp_avg], tr.opt.step_count,
-                    tr.bil_grids.detach().clone(), tr.bil_opt.exp_avg[0].clone(),
-                    [float(x) for x in losses], tr.bil_opt.step_count)
+                    tr.bil.grids.detach().clone(), tr.bil.opt.exp_avg[0].clone(),
+                    [float(x) for x in losses], tr.bil.opt.step_count)
         assert all(float((out[run][3][n] - start[n]).abs().max()) > 0 for n in range(4))
         if graph:
             g = tr._graph
@@ -170,7 +170,7 @@ def test_option_off_is_the_parent_step():
             tr.step(it)
         tr.sync()
         assert tr.graph_fallback is None, tr.graph_fallback
-        assert hasattr(tr, "bil_grids") == bool(kw.get("bilateral_grid"))
+        assert (tr.bil is not None) == bool(kw.get("bilateral_grid"))
         census.append(dict(tr._graph.census))
         tr.release_graph()
     assert census[0] == census[1], census

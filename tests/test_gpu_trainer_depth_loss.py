@@ -199,7 +199,7 @@ def test_one_step_means_gradient_matches_the_unfused_path(pose):
     assert part > 100.0 * bar, (part, bar)  # the test can tell a missing depth gradient
     assert err <= bar, (err, bar)
     if pose:
-        assert float(tr.pose_embeds[ci].abs().max()) > 0.0
+        assert float(tr.pose.embeds[ci].abs().max()) > 0.0
 
 
 def _run(graph, steps=6, **kw):
@@ -213,7 +213,7 @@ def _run(graph, steps=6, **kw):
                losses=torch.tensor([float(x.detach()) for x in losses]), tr=tr)
     if getattr(tr, "pose_opt", False):
         m, v = tr.moments()["pose_embeds"]
-        out["pose"] = dict(embeds=tr.pose_embeds.detach().clone(), m=m.clone(), v=v.clone())
+        out["pose"] = dict(embeds=tr.pose.embeds.detach().clone(), m=m.clone(), v=v.clone())
     return out
 
 

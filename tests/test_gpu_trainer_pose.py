@@ -107,8 +107,8 @@ def test_one_step_pose_gradient_matches_the_unfused_path():
     assert err <= bar, (err, bar)
     others = [r for r in range(4) if r != ci]
     assert not m[others].any() and not v[others].any()  # g = wd * 0 for the other rows
-    assert float(tr.pose_embeds[ci].abs().max()) > 0.0
-    assert not tr.pose_embeds[others].any()
+    assert float(tr.pose.embeds[ci].abs().max()) > 0.0
+    assert not tr.pose.embeds[others].any()
 
 
 def _run(graph, steps=6, **kw):
@@ -120,9 +120,9 @@ def _run(graph, steps=6, **kw):
     losses = [tr.step(it) for it in range(steps)]
     tr.sync()
     assert tr.graph_fallback is None, tr.graph_fallback
-    assert tr.pose_step_count == steps
+    assert tr.pose.step_count == steps
     m, v = tr.moments()["pose_embeds"]
-    out = dict(embeds=tr.pose_embeds.detach().clone(), m=m.clone(), v=v.clone(),
+    out = dict(embeds=tr.pose.embeds.detach().clone(), m=m.clone(), v=v.clone(),
                losses=torch.tensor([float(x.detach()) for x in losses]), tr=tr)
     return out
 
@@ -160,7 +160,7 @@ def test_refine_recaptures_and_keeps_the_pose_state():
     assert tr._graph.recaptures >= 2
     assert set(tr._graph.census) <= {"kernel", "empty"}, tr._graph.census
     n = tr.params["means"].shape[0]
-    assert tr._pose_ws.numel() >= 16 * ((n + 255) // 256)
+    assert tr.pose.ws.numel() >= 16 * ((n + 255) // 256)
     assert torch.isfinite(out["embeds"]).all() and torch.isfinite(out["losses"]).all()
     assert all(float(out["embeds"][k].abs().max()) > 0 for k in range(4))
     # every row's moments lived through the refines

@@ -67,16 +67,16 @@ def test_lr_schedule():
 
 def test_state_of_a_pose_opt_trainer():
     tr = _trainer(pose_opt=True, pose_noise=0.05, seed=7)
-    assert tr.pose_embeds.shape == (3, 9) and tr.pose_embeds.dtype == torch.float32
-    assert not tr.pose_embeds.any()
+    assert tr.pose.embeds.shape == (3, 9) and tr.pose.embeds.dtype == torch.float32
+    assert not tr.pose.embeds.any()
     m, v = tr.moments()["pose_embeds"]
     assert m.shape == v.shape == (3, 9) and not m.any() and not v.any()
     # the fixed perturbation: from the trainer's seed, N(0, pose_noise)
     again = _trainer(pose_opt=True, pose_noise=0.05, seed=7)
-    assert torch.equal(tr.pose_noise_table, again.pose_noise_table)
-    assert not torch.equal(tr.pose_noise_table,
-                           _trainer(pose_noise=0.05, seed=8).pose_noise_table)
-    assert 0.0 < float(tr.pose_noise_table.abs().max()) < 0.05 * 6
+    assert torch.equal(tr.pose.noise, again.pose.noise)
+    assert not torch.equal(tr.pose.noise,
+                           _trainer(pose_noise=0.05, seed=8).pose.noise)
+    assert 0.0 < float(tr.pose.noise.abs().max()) < 0.05 * 6
     # the pose draws leave the Gaussians' initialisation alone
     plain = _trainer(seed=7)
     for k in plain.params:

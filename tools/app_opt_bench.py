@@ -142,7 +142,7 @@ def part_step(steps, warmup, graph=True):
                          app_opt=on)
             if on:  # a trained module's last layer is not zero
                 g = torch.Generator().manual_seed(0)
-                tr.app_head[4].copy_((torch.randn(3, 64, generator=g) * 0.1).cuda())
+                tr.app.head[4].copy_((torch.randn(3, 64, generator=g) * 0.1).cuda())
             for it in range(warmup):
                 tr.step(it)
             tr.sync()
