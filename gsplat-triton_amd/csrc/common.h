@@ -19,7 +19,7 @@ constexpr int kWave = 64;
 // Per-thread last-error slot used by the C-ABI (see abi.cpp).
 void set_error(const char *fmt, ...);
 
-// GSPLAT_HIP_DBG / gsplat_hip_debug_set_flags (defined in rasterize16.hip;
+// GSPLAT_HIP_DBG / gsplat_hip_debug_set_flags (defined in rasterize16_plan.hip;
 // read by the 3DGS and the 2DGS rasterizers).
 int dbg_flags();
 

@@ -15,7 +15,7 @@
 // The backward walks the same records back to front, rebuilding T from
 // T_final, and reduces every per-Gaussian gradient across the wave with a
 // butterfly before one fp32 atomic per wave and field.
-#include "common.h"
+#include "raster16.h"
 #include "../../include/gsplat_hip.h"
 
 namespace gs {
@@ -288,38 +288,12 @@ int launch_bwd(const RasterArgs &a, int threads, hipStream_t st) {
 }
 
 inline bool supported_channels(int D) {
-  return D == 1 || D == 2 || D == 3 || D == 4 || D == 8 || D == 16 || D == 32;
+#define GS_CASE(n) if (D == n) return true;
+  GS_RASTER_CHANNELS(GS_CASE)
+#undef GS_CASE
+  return false;
 }
 
-}  // namespace gs
-
-namespace gs {
-int rasterize16_fwd(int C, int D, int W, int H, int tw, int th, const float *means2d,
-                    const float *conics, const float *colors, const float *opacities,
-                    const float *backgrounds, const uint8_t *masks, const int32_t *offsets,
-                    int64_t n_isects, const int64_t *n_isects_dev, const int32_t *flatten_ids,
-                    float *render_colors, float *render_alphas, int32_t *last_ids,
-                    const float *records, void *state, int64_t state_bytes, hipStream_t st);
-int rasterize16_record_floats(int D);
-int rasterize16_pack_records(int64_t G, int D, const float *means2d, const float *conics,
-                             const float *colors, const float *opacities, const int32_t *visible,
-                             const int32_t *vis_rank, float *records, hipStream_t st);
-int64_t rasterize16_fwd_state_bytes(int D, int n_tiles, int64_t n_isects);
-int rasterize16_prepare(int D, int C, int tw, int th, const int32_t *offsets, int64_t n_isects,
-                        const int64_t *n_isects_dev, void *state, int64_t state_bytes,
-                        hipStream_t st);
-int64_t rasterize16_bwd_workspace(int64_t G, int D, bool absgrad, int n_tiles, int64_t n_isects);
-int rasterize16_bwd(int C, int64_t G, int D, int W, int H, int tw, int th,
-                    const float *means2d, const float *conics, const float *colors,
-                    const float *opacities, const float *backgrounds, const uint8_t *masks,
-                    const int32_t *offsets, int64_t n_isects, const int64_t *n_isects_dev,
-                    const int32_t *flatten_ids, const float *render_alphas,
-                    const int32_t *last_ids, const float *v_render_colors,
-                    const float *v_render_alphas, float *v_means2d, float *v_conics,
-                    float *v_colors, float *v_opacities, float *v_abs, const float *render_colors,
-                    const float *records, const void *state, int64_t state_bytes,
-                    void *workspace, const int32_t *visible, const int32_t *vis_rank,
-                    hipStream_t st);
 }  // namespace gs
 
 using namespace gs;
@@ -327,7 +301,8 @@ using namespace gs;
 extern "C" int gsplat_hip_rasterize_supported_channels(int D) { return supported_channels(D); }
 
 // 16x16 tiles (the gsplat default) run the wave-per-tile kernels of
-// rasterize16.hip; other tile sizes run the workgroup-per-tile kernels here.
+// rasterize16.hip (its entries: raster16.h); other tile sizes run the
+// workgroup-per-tile kernels here.
 extern "C" int64_t gsplat_hip_rasterize_fwd_state_bytes(int C, int D, int tile_size,
                                                         int tile_width, int tile_height,
                                                         int64_t n_isects) {
@@ -406,15 +381,9 @@ extern "C" int gsplat_hip_rasterize_fwd(int C, int D, int width, int height, int
                            n_isects_device, flatten_ids, render_colors, render_alphas, last_ids,
                            records, state, state_bytes, st);
   const int thr = block_threads(tile_size);
-  switch (D) {
-    case 1: return launch_fwd<1>(a, thr, st);
-    case 2: return launch_fwd<2>(a, thr, st);
-    case 3: return launch_fwd<3>(a, thr, st);
-    case 4: return launch_fwd<4>(a, thr, st);
-    case 8: return launch_fwd<8>(a, thr, st);
-    case 16: return launch_fwd<16>(a, thr, st);
-    case 32: return launch_fwd<32>(a, thr, st);
-  }
+#define GS_CASE(n) if (D == n) return launch_fwd<n>(a, thr, st);
+  GS_RASTER_CHANNELS(GS_CASE)
+#undef GS_CASE
   return 1;
 }
 
@@ -467,14 +436,8 @@ extern "C" int gsplat_hip_rasterize_bwd(
   a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors = v_colors;
   a.v_opacities = v_opacities; a.v_means2d_abs = v_means2d_abs;
   const int thr = block_threads(tile_size);
-  switch (D) {
-    case 1: return launch_bwd<1>(a, thr, st);
-    case 2: return launch_bwd<2>(a, thr, st);
-    case 3: return launch_bwd<3>(a, thr, st);
-    case 4: return launch_bwd<4>(a, thr, st);
-    case 8: return launch_bwd<8>(a, thr, st);
-    case 16: return launch_bwd<16>(a, thr, st);
-    case 32: return launch_bwd<32>(a, thr, st);
-  }
+#define GS_CASE(n) if (D == n) return launch_bwd<n>(a, thr, st);
+  GS_RASTER_CHANNELS(GS_CASE)
+#undef GS_CASE
   return 1;
 }

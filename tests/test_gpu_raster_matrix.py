@@ -1,8 +1,8 @@
 """GPU: every instantiation of the rasterizer against the float64 oracle.
 
 The rasterizer is compiled in two families -- wave-per-tile kernels for 16x16
-tiles (csrc/rasterize16.hip) and workgroup-per-tile kernels for the other
-tile sizes (csrc/rasterize.hip) -- each for D in {1, 2, 3, 4, 8, 16, 32}, the
+tiles (csrc/rasterize16.hip, planned by rasterize16_plan.hip) and
+workgroup-per-tile kernels for the other tile sizes (csrc/rasterize.hip) -- each for D in {1, 2, 3, 4, 8, 16, 32}, the
 backward with and without absgrad; the 16x16 family also has a record and an
 array-gather path, a split forward and a chunked backward.  Scenes, oracle
 runs and bars: tests/raster_cases.py; tests/test_raster_cases_host.py shows
