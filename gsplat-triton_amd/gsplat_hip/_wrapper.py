@@ -204,9 +204,10 @@ class _FullyFusedProjectionPacked(torch.autograd.Function):
         depths = torch.empty(nnz, device=dev)
         conics = torch.empty((nnz, 3), device=dev)
         comps = torch.empty(nnz, device=dev) if calc_compensations else None
-        _lib.call("gsplat_hip_projection_packed_fwd", C, N, *args, _ptr(ws), _ptr(camera_ids),
-                  _ptr(gaussian_ids), _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics),
-                  _ptr(comps), _stream())
+        if nnz > 0:  # every pair culled: empty outputs have null pointers, which the entry refuses
+            _lib.call("gsplat_hip_projection_packed_fwd", C, N, *args, _ptr(ws), _ptr(camera_ids),
+                      _ptr(gaussian_ids), _ptr(radii), _ptr(means2d), _ptr(depths), _ptr(conics),
+                      _ptr(comps), _stream())
         ctx.save_for_backward(camera_ids, gaussian_ids, means, quats, scales, viewmats, Ks,
                               conics, comps)
         ctx.width, ctx.height, ctx.eps2d = int(width), int(height), float(eps2d)

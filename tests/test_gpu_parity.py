@@ -3,7 +3,10 @@ and the CPU oracle.  Tolerances follow the reference's own tests
 (triton_tests/test_fused_proj.py:116-162, test_sh.py:25-37,
 test_isect.py:86-89 [exact], test_ras2pix.py:132-161).
 The SH goldens here anchor the kernels to the reference at 1e-4; the float64
-bounds of every SH instantiation are in tests/test_gpu_sh_matrix.py."""
+bounds of every SH instantiation are in tests/test_gpu_sh_matrix.py.
+The projection goldens here anchor the kernels to the reference at its
+tolerances; the float64 bounds of every projection instantiation are in
+tests/test_gpu_proj_matrix.py."""
 
 import math
 
