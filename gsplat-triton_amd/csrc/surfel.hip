@@ -228,11 +228,18 @@ GS_INLINE void stage(float *slot, const Gathered<D> &r, int32_t idx) {
 }
 
 // Forward record: the ray-splat cross product is linear in the pixel centre,
-//   (px w - u) x (py w - v) = px (v x w) + py (w x u) + (u x v),
-// so the staging lane precomputes A = v x w, B = w x u, Cc = u x v (x and y
-// components pre-scaled by sqrt(log2(e) / 2), making |s|^2 come out as
-// sigma * log2(e) directly) and smax = log2(255 opacity): a pixel hits iff
-// min(g3, g2) * log2(e) / 2 <= smax and the exponential is a bare exp2.
+//   (px w - u) x (py w - v) = Cc - dx (v x w) - dy (w x u),
+// with (dx, dy) = mean2d - pixel (the offsets g2 needs anyway) and Cc the
+// cross product at the 2-D mean, (x w - u) x (y w - v).  The staging lane
+// precomputes A = v x w, B = w x u and Cc (x and y components pre-scaled by
+// sqrt(log2(e) / 2), making |s|^2 come out as sigma * log2(e) directly) and
+// smax = log2(255 opacity): a pixel hits iff min(g3, g2) * log2(e) / 2 <= smax
+// and the exponential is a bare exp2.  Anchored at the mean the form cancels
+// as the plain one does (and like g2 it needs a finite mean2d, which the
+// projection always writes: with a NaN or infinite one the record contributes
+// nothing, where the origin form left g3 alone); anchored at the image origin (Cc = u x v, the pixel
+// entering with its absolute coordinates) it lost 6x in alpha to cancellation
+// (tests/test_gpu_surfel_matrix.py).
 template <int D>
 struct FRec {
   static constexpr int X = 0, Y = 1, OP = 2, IDX = 3, A = 4, B = 7, CC = 10, SMAX = 13, NRM = 14,
@@ -242,6 +249,24 @@ struct FRec {
 };
 
 constexpr float kSqrtHalfLog2e = 0.84932180028801907f;  // sqrt(log2(e) / 2)
+
+// Cc of the forward record: (x w - u) x (y w - v) at the 2-D mean (x, y).  The
+// roundings are spelled out (one fma per difference, a product and an fma per
+// component) so that stage_fwd and pack_srec_kernel form the same bits: the
+// differences cancel, and another contraction of them moves a needle's s by
+// more than the two forwards may differ.
+GS_INLINE void cross_at_mean(const float *m, float x, float y, float (&c)[3]) {
+  float hu[3], hv[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    hu[i] = __builtin_fmaf(x, m[6 + i], -m[i]);
+    hv[i] = __builtin_fmaf(y, m[6 + i], -m[3 + i]);
+  }
+  const float t0 = hu[2] * hv[1], t1 = hu[0] * hv[2], t2 = hu[1] * hv[0];
+  c[0] = __builtin_fmaf(hu[1], hv[2], -t0);
+  c[1] = __builtin_fmaf(hu[2], hv[0], -t1);
+  c[2] = __builtin_fmaf(hu[0], hv[1], -t2);
+}
 
 template <int D>
 GS_INLINE void stage_fwd(float *slot, const Gathered<D> &r, int32_t idx) {
@@ -259,9 +284,11 @@ GS_INLINE void stage_fwd(float *slot, const Gathered<D> &r, int32_t idx) {
   v_[R::B + 0] = k * (w[1] * u[2] - w[2] * u[1]);
   v_[R::B + 1] = k * (w[2] * u[0] - w[0] * u[2]);
   v_[R::B + 2] = w[0] * u[1] - w[1] * u[0];
-  v_[R::CC + 0] = k * (u[1] * v[2] - u[2] * v[1]);
-  v_[R::CC + 1] = k * (u[2] * v[0] - u[0] * v[2]);
-  v_[R::CC + 2] = u[0] * v[1] - u[1] * v[0];
+  float cm[3];
+  cross_at_mean(r.m, r.xy.x, r.xy.y, cm);
+  v_[R::CC + 0] = k * cm[0];
+  v_[R::CC + 1] = k * cm[1];
+  v_[R::CC + 2] = cm[2];
   v_[R::SMAX] = __builtin_amdgcn_logf(255.f * r.op);  // log2
 #pragma unroll
   for (int i = 0; i < 3; ++i) v_[R::NRM + i] = r.nrm[i];
@@ -316,9 +343,9 @@ GS_INLINE Hit eval_hit(const float *m, float x, float y, float op, float px, flo
 }
 
 // One record into one pixel: the forward's compositing step.  The pixel centre
-// is (fx, fy); the caller passes the fx part of the linear ray-splat form
-// (FRec), r*b = fx * A + Cc, and dx2 = (x - fx)^2, which the two pixels of a
-// lane share.  LEAN: only the colours, T and the last id.  Called by
+// is (fx, fy); the caller passes the x part of the linear ray-splat form
+// (FRec), r*b = Cc - (x - fx) A, and dx2 = (x - fx)^2, which the two pixels of
+// a lane share.  LEAN: only the colours, T and the last id.  Called by
 // fwd2_kernel and fwd2s_kernel; fwd_kernel has the statements written out
 // (called from it: more VGPRs; profiles/surfel_split/README.md).
 template <int D, bool LEAN>
@@ -328,12 +355,12 @@ GS_INLINE void blend_pixel(bool &done, float &T, float (&col)[D], float (&nrm)[3
                            float dx2, float y, float op, float smax, const float *c, float n0,
                            float n1, float n2, int32_t idx) {
   if (done) return;
-  const float rx = fy * bx + rxb;
-  const float ry = fy * by + ryb;
-  const float rz = fy * bz + rzb;
+  const float dy = y - fy;
+  const float rx = rxb - dy * bx;
+  const float ry = ryb - dy * by;
+  const float rz = rzb - dy * bz;
   const float iz = __builtin_amdgcn_rcpf(rz);
   const float g3 = (rx * rx + ry * ry) * (iz * iz);
-  const float dy = y - fy;
   const float g2 = kLog2e * (dx2 + dy * dy);
   const float m = fminf(g3, g2);  // sigma * log2(e)
   if (rz != 0.f && m <= smax) {
@@ -437,12 +464,12 @@ __global__ void __launch_bounds__(1024) fwd_kernel(RasterArgs a) {
       float r[R::NF];
       read_f4<R::NF>(q + t * R::NF, r);
       if (!done) {  // blend_pixel<D, false>, written out (see its comment)
-        const float rx = fx * r[R::A] + fy * r[R::B] + r[R::CC];
-        const float ry = fx * r[R::A + 1] + fy * r[R::B + 1] + r[R::CC + 1];
-        const float rz = fx * r[R::A + 2] + fy * r[R::B + 2] + r[R::CC + 2];
+        const float dx = r[R::X] - fx, dy = r[R::Y] - fy;
+        const float rx = r[R::CC] - dx * r[R::A] - dy * r[R::B];
+        const float ry = r[R::CC + 1] - dx * r[R::A + 1] - dy * r[R::B + 1];
+        const float rz = r[R::CC + 2] - dx * r[R::A + 2] - dy * r[R::B + 2];
         const float iz = __builtin_amdgcn_rcpf(rz);
         const float g3 = (rx * rx + ry * ry) * (iz * iz);
-        const float dx = r[R::X] - fx, dy = r[R::Y] - fy;
         const float g2 = kLog2e * (dx * dx + dy * dy);
         const float m = fminf(g3, g2);  // sigma * log2(e)
         if (rz != 0.f && m <= r[R::SMAX]) {
@@ -527,9 +554,9 @@ __global__ void __launch_bounds__(128) fwd2_kernel(RasterArgs a) {
     for (int t = 0; t < n; ++t) {
       float r[R::NF];
       read_f4<R::NF>(q + t * R::NF, r);
-      const float rxb = fx * r[R::A] + r[R::CC], ryb = fx * r[R::A + 1] + r[R::CC + 1],
-                  rzb = fx * r[R::A + 2] + r[R::CC + 2];
       const float dx = r[R::X] - fx, dx2 = dx * dx;
+      const float rxb = r[R::CC] - dx * r[R::A], ryb = r[R::CC + 1] - dx * r[R::A + 1],
+                  rzb = r[R::CC + 2] - dx * r[R::A + 2];
 #pragma unroll
       for (int k = 0; k < 2; ++k)
         blend_pixel<D, false>(done[k], T[k], col[k], nrm[k], distort[k], acc_vd[k], median[k],
@@ -638,7 +665,7 @@ namespace srec {
 // floats of a record
 constexpr int NF = 32;
 constexpr int X = 0, Y = 1, OP = 2, SMAX = 3,   // chunk 0
-    AZ = 4, BZ = 5, CZ = 6,                      // chunk 1 (z parts: unscaled)
+    AZ = 4, BZ = 5, CZ = 6, CZM = 7,             // chunk 1 (z parts: unscaled; CZM: at the mean)
     BOX = 8,                                     // chunk 2: xlo, xhi, ylo, yhi
     U0X = 12, U0Y = 13, U1X = 14, U1Y = 15,      // chunk 3: v x w, w x u (unscaled)
     U2X = 16, U2Y = 17, NRM0 = 18, NRM1 = 19,    // chunk 4: u x v
@@ -700,8 +727,11 @@ pack_srec_kernel(int64_t G, const float *__restrict__ means2d, const float *__re
   r[AY] = k * (v[2] * w[0] - v[0] * w[2]);
   r[BX] = k * (w[1] * u[2] - w[2] * u[1]);
   r[BY] = k * (w[2] * u[0] - w[0] * u[2]);
-  r[CX] = k * (u[1] * v[2] - u[2] * v[1]);
-  r[CY] = k * (u[2] * v[0] - u[0] * v[2]);
+  float cm[3];  // Cc of the compositing form: at the 2-D mean, as stage_fwd
+  cross_at_mean(m, r[X], r[Y], cm);
+  r[CX] = k * cm[0];
+  r[CY] = k * cm[1];
+  r[CZM] = cm[2];
   r[NRM0] = nrm[3 * g];
   r[NRM1] = nrm[3 * g + 1];
   r[NRM2] = nrm[3 * g + 2];
@@ -784,7 +814,7 @@ GS_INLINE void srec_load_blend(const float *rec, int32_t g, SBlend<D> &r) {
   cfloat_t *p = (cfloat_t *)(rec) + (int64_t)srec::NF * g;
   using namespace srec;
   r.x = p[X]; r.y = p[Y]; r.op = p[OP]; r.smax = p[SMAX];
-  r.az = p[AZ]; r.bz = p[BZ]; r.cz = p[CZ];
+  r.az = p[AZ]; r.bz = p[BZ]; r.cz = p[CZM];
   r.n0 = p[NRM0]; r.n1 = p[NRM1];
   r.ax = p[AX]; r.ay = p[AY]; r.bx = p[BX]; r.by = p[BY];
   r.cx = p[CX]; r.cy = p[CY]; r.n2 = p[NRM2];
@@ -822,8 +852,8 @@ __global__ void __launch_bounds__(128) fwd2s_kernel(RasterArgs a, const float *_
   }
   // one record into both pixels of the lane
   auto blend = [&](const SBlend<D> &r, int32_t idx) {
-    const float rxb = fx * r.ax + r.cx, ryb = fx * r.ay + r.cy, rzb = fx * r.az + r.cz;
     const float dx = r.x - fx, dx2 = dx * dx;
+    const float rxb = r.cx - dx * r.ax, ryb = r.cy - dx * r.ay, rzb = r.cz - dx * r.az;
 #pragma unroll
     for (int k = 0; k < 2; ++k)
       blend_pixel<D, LEAN>(done[k], T[k], col[k], nrm[k], distort[k], acc_vd[k], median[k], cur[k],
@@ -1489,6 +1519,16 @@ int lean_stride(int D, int absgrad) {  // Fields<D, ABS, true>::S
   return 16 * ((nf + 15) / 16);
 }
 
+// LDS of the forward's per-wave queues (64 records of FRec<D>::NF floats each)
+// and what a gfx950 CU has.
+constexpr size_t kLdsPerCu = 160 * 1024;
+size_t fwd_queue_bytes(int D, int waves) {
+#define GS_CASE(n) if (D == n) return (size_t)waves * 64 * FRec<n>::NF * sizeof(float);
+  GS_SURFEL_CHANNELS(GS_CASE)
+#undef GS_CASE
+  return 0;
+}
+
 int check_tiles(int C, int W, int H, int ts, int tw, int th) {
   GS_REQUIRE(C >= 0 && W >= 0 && H >= 0, "rasterize_2dgs: negative sizes");
   GS_REQUIRE(ts >= 1 && ts <= 32, "rasterize_2dgs: tile_size %d not in [1, 32]", ts);
@@ -1531,6 +1571,13 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
                                flatten_ids),
              "rasterize_2dgs_fwd: null pointer argument");
   GS_REQUIRE(((uintptr_t)means2d & 7) == 0, "rasterize_2dgs_fwd: means2d must be 8-B aligned");
+  const int waves = (tile_size * tile_size + 63) / 64;
+  // fwd_kernel keeps a queue per wave: 32x32 tiles of 32 or 33 channels would
+  // need 208 KiB (refused here, before anything is launched)
+  GS_REQUIRE(records || tile_size == 16 || fwd_queue_bytes(D, waves) <= kLdsPerCu,
+             "rasterize_2dgs_fwd: tile_size %d with %d channels needs %zu B of LDS, the device "
+             "has %zu: use a smaller tile size",
+             tile_size, D, fwd_queue_bytes(D, waves), kLdsPerCu);
   RasterArgs a{};
   a.C = C; a.W = width; a.H = height; a.ts = tile_size; a.tw = tile_width; a.th = tile_height;
   a.n_tiles = n_tiles; a.n_isects = n_isects; a.n_dev = n_isects_device;
@@ -1540,7 +1587,6 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
   a.render_colors = render_colors; a.render_alphas = render_alphas;
   a.render_normals = render_normals; a.render_distort = render_distort;
   a.render_median = render_median; a.last_ids = last_ids; a.median_ids = median_ids;
-  const int waves = (tile_size * tile_size + 63) / 64;
   hipStream_t st = (hipStream_t)stream;
   unsigned grid_t = (unsigned)n_tiles;
   if (tile_order && n_tiles > 0) {  // written here, read by this launch and the backward
@@ -1567,7 +1613,7 @@ extern "C" int gsplat_hip_rasterize_2dgs_fwd(
   }
 #define GS_CASE(n)                                                                            \
   if (D == n) {                                                                               \
-    const size_t lds = (size_t)waves * 64 * Rec<n>::NF * sizeof(float);                       \
+    const size_t lds = fwd_queue_bytes(n, waves);                                             \
     if (px2)                                                                                  \
       hipLaunchKernelGGL(fwd2_kernel<n>, dim3(grid_t), dim3(128), lds / 2, st, a);           \
     else                                                                                      \

@@ -20,13 +20,21 @@ Pinning:
     reference test's scene and on random scenes (tests/golden/make_golden_2dgs.py
     -> tests/golden/proj2dgs_*.npz), at the reference test's tolerances
     (tests/test_2dgs.py:77-122).
-  * rasterization: PARITY UNPINNED against reference outputs -- the
-    reference's only CPU rasterizer for 2DGS (`_rasterize_to_pixels_2dgs`,
+  * rasterization: no reference outputs exist to pin it -- the reference's
+    only CPU rasterizer for 2DGS (`_rasterize_to_pixels_2dgs`,
     _torch_impl_2dgs.py:179-272) needs the CUDA extension
     (`rasterize_to_indices_in_range_2dgs`) and nerfacc, neither of which runs
     here, and the repository ships no 2DGS render fixtures.  The forward is a
-    line-by-line restatement; the backward is checked against torch autograd
-    of an independent torch restatement of the forward (tests/test_surfel_oracle.py).
+    line-by-line restatement.  It is pinned by the float64 oracle of
+    tests/surfel_cases.py, written from the definitions and itself checked
+    against float64 finite differences (tests/test_surfel_cases_host.py): on
+    every case of that matrix this float32 forward reproduces the float64
+    last ids, median ids and contributor sets exactly and its images to
+    4.5e-5 of the largest value (needles; 5e-6 otherwise), and the
+    hand-derived backward agrees with float64 autograd to 4.7e-4 of the
+    largest gradient (the bars of tests/golden/surfel_matrix.npz, which this
+    oracle helps to set).  tests/test_surfel_oracle.py still checks the
+    backward against float32 autograd of an independent torch restatement.
 
 Deliberate, documented deviations (same as the HIP path):
   * culled projection entries are zeros (the reference leaves them
@@ -195,10 +203,12 @@ def _eval(m, x, y, op, px, py):
 
 
 def raster2dgs_fwd(means2d, ray_transforms, colors, opacities, normals, backgrounds, masks, W, H,
-                   ts, offsets, flatten_ids):
+                   ts, offsets, flatten_ids, contrib=None):
     """RasterizeToPixels2DGSFwd.cu:18-452.  Returns render_colors[C,H,W,D],
     alphas[C,H,W,1], normals[C,H,W,3], distort[C,H,W,1], median[C,H,W,1],
-    last_ids i32[C,H,W], median_ids i32[C,H,W]."""
+    last_ids i32[C,H,W], median_ids i32[C,H,W].  contrib (a dict, or None):
+    receives each pixel's contributor set as ncon i64[C,H,W] (its size) and
+    jsum (the sum of its squared isect indices)."""
     C, th, tw = offsets.shape
     D = colors.shape[-1]
     m2 = _f(means2d).reshape(-1, 2)
@@ -215,6 +225,7 @@ def raster2dgs_fwd(means2d, ray_transforms, colors, opacities, normals, backgrou
     om = np.zeros((C, H, W, 1), f32)
     ol = np.zeros((C, H, W), np.int32)
     omi = np.zeros((C, H, W), np.int32)
+    ncon, jsum = np.zeros((C, H, W), np.int64), np.zeros((C, H, W), np.int64)
     ly, lx = np.meshgrid(np.arange(ts), np.arange(ts), indexing="ij")
     for t in range(C * th * tw):
         c, rem = divmod(t, th * tw)
@@ -238,6 +249,7 @@ def raster2dgs_fwd(means2d, ray_transforms, colors, opacities, normals, backgrou
         med = np.zeros(P, f32)
         cur = np.zeros(P, np.int32)
         mid = np.zeros(P, np.int32)
+        nc, js = np.zeros(P, np.int64), np.zeros(P, np.int64)
         for j in range(starts[t], ends[t]):
             if done.all():
                 break
@@ -259,6 +271,8 @@ def raster2dgs_fwd(means2d, ray_transforms, colors, opacities, normals, backgrou
             med = np.where(upd, depth, med).astype(f32)
             mid = np.where(upd, j, mid).astype(np.int32)
             cur = np.where(act, j, cur).astype(np.int32)
+            nc += act
+            js += act * (int(j) * int(j))
             T = np.where(act, nT, T).astype(f32)
         if backgrounds is not None:
             col = col + T[:, None] * _f(backgrounds)[c][None]
@@ -269,6 +283,9 @@ def raster2dgs_fwd(means2d, ray_transforms, colors, opacities, normals, backgrou
         om[c, pyi, pxi, 0] = med
         ol[c, pyi, pxi] = cur
         omi[c, pyi, pxi] = mid
+        ncon[c, pyi, pxi], jsum[c, pyi, pxi] = nc, js
+    if contrib is not None:
+        contrib.update(ncon=ncon, jsum=jsum)
     return oc, oa, on, od, om, ol, omi
 
 
