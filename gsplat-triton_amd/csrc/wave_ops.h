@@ -91,6 +91,14 @@ GS_INLINE int rs_field(int lane) {
          (((lane >> 2) & 1) << 3);
 }
 
+// Butterfly sum of a double over the 64 lanes (the float form is common.h's);
+// every lane ends with the same total, added in the same order in every run.
+GS_INLINE double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+  return v;
+}
+
 GS_INLINE void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();

@@ -24,6 +24,7 @@ from ._wrapper_indices import (
 )
 from .appearance import appearance_colors
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
+from .color_correct import color_correct
 from .compression import PngCompression
 from .depth_loss import sparse_depth_loss
 from .io import load_ply, save_ply
@@ -53,6 +54,7 @@ __all__ = [
     "pose_adjust",
     "appearance_colors",
     "PngCompression",
+    "color_correct",
     "quat_scale_to_covar_preci",
     "world_to_cam",
     "proj",

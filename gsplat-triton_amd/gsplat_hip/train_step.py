@@ -113,6 +113,7 @@ from . import densify
 from .densify import DefaultStrategyConfig
 from . import mcmc as _mcmc
 from .mcmc import MCMCStrategyConfig
+from .color_correct import color_correct as _color_correct
 from .losses import FusedAdam, l1_ssim_loss, ssim_and_l1
 from . import _lib, _wrapper
 from .appearance import AppearanceOptimizer
@@ -1286,7 +1287,8 @@ class Trainer:
 
     # ---------------------------------------------------------------- eval
     @torch.no_grad()
-    def evaluate(self, cameras=None, viewmats=None, Ks=None, images=None, masks=None):
+    def evaluate(self, cameras=None, viewmats=None, Ks=None, images=None, masks=None,
+                 color_correct=False):
         """simple_trainer.py:854-932's eval metrics: render each camera,
         clamp to [0, 1], PSNR (data range 1) and SSIM (11x11 Gaussian, the
         fused "valid" SSIM of the loss) against the target, averaged.  Either
@@ -1295,7 +1297,15 @@ class Trainer:
         computed (its network weights are a download).  A trainer with masks
         zeroes each pool camera's render outside its mask before the metrics
         (simple_trainer.py:871-884 passes the masks to the render); `masks`
-        [M,H,W] bool does so for the explicit form.  No background is added."""
+        [M,H,W] bool does so for the explicit form.  No background is added.
+
+        color_correct=True adds `cc_psnr` and `cc_ssim` (simple_trainer.py:
+        906-909, reported there for bilateral-grid runs): each clamped render,
+        after the mask, is first warped onto its target by
+        gsplat_hip.color_correct, which takes out the per-image exposure and
+        white balance that a bilateral grid or app_opt run leaves to the image;
+        the same metrics, averaged the same way.  Masked pixels are 0, below
+        the fit's clipping threshold, so they take no part in the fit."""
         self.sync()
         if viewmats is None:
             idx = list(range(len(self.viewmats))) if cameras is None else list(cameras)
@@ -1307,7 +1317,7 @@ class Trainer:
                 raise ValueError(f"evaluate: masks [{len(viewmats)}, {self.height}, "
                                  f"{self.width}], got {list(masks.shape)}")
             masks = masks.to(self.device).bool()
-        psnrs, ssims = [], []
+        psnrs, ssims, cc_psnrs, cc_ssims = [], [], [], []
         saved = self.viewmats, self.Ks
         try:
             self.viewmats, self.Ks = viewmats.to(self.device), Ks.to(self.device)
@@ -1323,21 +1333,30 @@ class Trainer:
                 mse = torch.mean((colors - gt) ** 2)
                 psnrs.append(float(-10.0 * torch.log10(mse)))
                 ssims.append(float(ssim_and_l1(colors, gt)[0]))
+                if color_correct:
+                    cc = _color_correct(colors, gt)
+                    cc_psnrs.append(float(-10.0 * torch.log10(torch.mean((cc - gt) ** 2))))
+                    cc_ssims.append(float(ssim_and_l1(cc, gt)[0]))
         finally:
             self.viewmats, self.Ks = saved
             self.__dict__.pop("_wcam_cache", None)
-        return {"psnr": sum(psnrs) / len(psnrs), "ssim": sum(ssims) / len(ssims),
-                "num_images": len(psnrs)}
+        out = {"psnr": sum(psnrs) / len(psnrs), "ssim": sum(ssims) / len(ssims),
+               "num_images": len(psnrs)}
+        if color_correct:
+            out["cc_psnr"] = sum(cc_psnrs) / len(cc_psnrs)
+            out["cc_ssim"] = sum(cc_ssims) / len(cc_ssims)
+        return out
 
     @torch.no_grad()
     def evaluate_compressed(self, compress_dir, cameras=None, viewmats=None, Ks=None,
-                            images=None, compression=None):
+                            images=None, compression=None, color_correct=False):
         """simple_trainer.py's run_compression (compression="png"): compress the
         current parameters into `compress_dir` (compression.PngCompression, or
         the instance given), decompress them and evaluate what came back --
         evaluate()'s cameras, render path and metrics (app_opt: the zero
         embedding), plus `compressed_bytes` (the sum of the file sizes in
-        `compress_dir`) and `num_GS` (the n^2 Gaussians of the grid).  The
+        `compress_dir`) and `num_GS` (the n^2 Gaussians of the grid);
+        `color_correct` is evaluate()'s.  The
         trainer's parameters, optimizer state and captured step are not
         touched: the decompressed splats stand in only for these renders."""
         _refuse("compression", {"gaussian_shard": self.gshard,
@@ -1356,7 +1375,7 @@ class Trainer:
         try:
             self.params = {k: splats[k].to(self.device, saved[k].dtype).contiguous()
                            for k in saved}
-            out = self.evaluate(cameras, viewmats, Ks, images)
+            out = self.evaluate(cameras, viewmats, Ks, images, color_correct=color_correct)
             out["num_GS"] = int(self.params["means"].shape[0])
         finally:
             self.params = saved

@@ -70,7 +70,9 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_l1_ssim_loss_masked_fwd / _bwd (the 3DGS trainer's per-image
  *     masks and random background, composed in the loss kernel);
  *     gsplat_hip_tsdf_integrate, gsplat_hip_mc_count / _emit / _table /
- *     _workspace_bytes (mesh export). */
+ *     _workspace_bytes (mesh export);
+ *     gsplat_hip_color_correct and gsplat_hip_color_correct_workspace_bytes
+ *     (colour-corrected evaluation). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1492,6 +1494,39 @@ int gsplat_hip_mc_emit(int nx, int ny, int nz, float ox, float oy, float oz, flo
                        const void *workspace, int64_t n_vertices, int64_t n_faces,
                        float *vertices, float *vertex_colors, int32_t *faces, void *stream);
 int gsplat_hip_mc_table(int8_t *out);
+
+/* ---------------------------------------------------------------------------
+ * Colour-corrected evaluation (ABI 38, new entries only; examples/
+ * lib_bilagrid.py:56-126 color_correct, csrc/color_correct.hip): the render is
+ * warped onto the ground truth by a quadratic colour map fitted by least
+ * squares over the unclipped pixels, num_iters times.
+ * img, ref, out: [P,3] float32 in [0, 1], contiguous, 16-B aligned; out must
+ * not overlap img.  With lo = (float)eps, hi = (float)(1 - eps) and
+ * unclipped(z) = lo <= z <= hi (compared in float32), x = img, and per
+ * iteration:
+ *   a(x) = [x0x0, x0x1, x0x2, x1x1, x1x2, x2x2, x0, x1, x2, 1]
+ *   per channel c, over the rows p with unclipped(img[p,c]), unclipped(x[p,c])
+ *   and unclipped(ref[p,c]):  G_c = sum a a^T,  h_c = sum a ref[p,c];
+ *   G_c w_c = h_c by Cholesky of D^-1/2 G_c D^-1/2, D = diag(G_c);
+ *   x[p,:] = clip(a(x_p) . [w_0 w_1 w_2], 0, 1) for every row.
+ * G_c, h_c, the solve and the warp are float64; x is rounded to float32 once
+ * per iteration (it is held in `out`).  A channel with fewer than 10 rows, a
+ * diagonal entry that is not positive or a pivot below 1e-10 keeps its values
+ * for that iteration (w_c = the unit vector of linear term c) and sets
+ * fallbacks[it * 3 + c] = 1, else 0 (int32 [num_iters * 3], may be NULL).
+ * The reference solves each system with torch.linalg.lstsq (QR) in the input's
+ * precision and asserts on a system it cannot solve.
+ * Three launches per iteration (sums, solve, warp); the host reads nothing in
+ * between.  No atomics, the number of workgroups depends on P alone:
+ * bit-identical between calls.  num_iters = 0 copies img to out.
+ * Status 1: a null pointer, P < 1, num_iters < 0, eps outside (0, 0.5), a
+ * misaligned or overlapping buffer.
+ *   _workspace_bytes: of uninitialised memory, 16-B aligned, for P rows (the
+ *   workgroups' partial sums and the 10 x 3 float64 map); 0 for P < 1. */
+int64_t gsplat_hip_color_correct_workspace_bytes(int64_t P);
+int gsplat_hip_color_correct(int64_t P, const float *img, const float *ref, int num_iters,
+                             double eps, float *out, void *workspace, int32_t *fallbacks,
+                             void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
