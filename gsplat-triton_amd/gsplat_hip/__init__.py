@@ -32,6 +32,7 @@ from .losses import geometry_loss_2dgs
 from .mesh import TSDFVolume, save_mesh_ply
 from .pose import pose_adjust
 from .rendering import depth_to_normal, rasterization, rasterization_2dgs
+from .transform import merge_splats, rotate_sh, sh_rotation_matrices, transform_splats
 from .undistort import remap_bilinear, undistort_images
 
 __all__ = [
@@ -71,5 +72,9 @@ __all__ = [
     "load_ply",
     "TSDFVolume",
     "save_mesh_ply",
+    "transform_splats",
+    "rotate_sh",
+    "sh_rotation_matrices",
+    "merge_splats",
 ]
 __version__ = "0.1.0"

@@ -223,6 +223,11 @@ _SIGS = {
     "gsplat_hip_kmeans_update": (_i32, [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_color_correct_workspace_bytes": (_i64, [_i64]),
     "gsplat_hip_color_correct": (_i32, [_i64, _p, _p, _i32, _d, _p, _p, _p, _p]),
+    "gsplat_hip_splat_xform_record_floats": (_i32, [_i32]),
+    "gsplat_hip_splat_xform_prepare": (_i32, [_i64, _i32, _p, _p, _p, _p]),
+    "gsplat_hip_splat_xform_apply": (_i32, [_i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                            _p, _p, _p, _p]),
+    "gsplat_hip_splat_xform_rotate_sh": (_i32, [_i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "gsplat_hip_undistort_u8_f32": (_i32, [_i32, _i32, _i32, _p] + [_d] * 12
                                     + [_i32, _i32, _i32, _i32, _i32, _f, _p, _p]),
     "gsplat_hip_remap_u8_f32": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _i32, _f, _p, _p]),

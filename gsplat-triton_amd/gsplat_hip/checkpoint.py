@@ -236,17 +236,27 @@ def load(tr, paths, resume=True):
 
 
 @torch.no_grad()
-def save_ply(tr, path, sh_degree=None):
+def save_ply(tr, path, sh_degree=None, transform=None):
     """Trainer.save_ply: the parameters as a PLY file (io.save_ply); app_opt:
-    the colours baked as simple_trainer.py:753-763 does."""
+    the colours baked as simple_trainer.py:753-763 does.  `transform`: a [4,4]
+    similarity the Gaussians are moved by first (transform.transform_splats);
+    the baked colours of app_opt are taken before the move and keep their
+    values."""
     from .io import save_ply as _save_ply
     refuse(tr, "save_ply (checkpoint)")
     p = {k: v.data for k, v in tr.synced_params().items()}
     if not tr.app_opt:
+        if transform is not None:
+            from .transform import transform_splats
+            p = transform_splats(p, transform)
         return _save_ply(p, path)
     from .appearance import appearance_colors
     deg = tr.sh_degree if sh_degree is None else int(sh_degree)
     zeros = torch.zeros_like(p["means"])
     colors = appearance_colors(p["features"], p["colors"], None, zeros,
                                torch.zeros(1, 3, device=zeros.device), tr.app.head, deg)[0]
-    return _save_ply({k: p[k] for k in ("means", "scales", "quats", "opacities")}, path, colors)
+    geom = {k: p[k] for k in ("means", "scales", "quats", "opacities")}
+    if transform is not None:
+        from .transform import transform_splats
+        geom = transform_splats(geom, transform)
+    return _save_ply(geom, path, colors)

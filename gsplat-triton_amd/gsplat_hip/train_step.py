@@ -1530,13 +1530,21 @@ class Trainer:
         from . import checkpoint
         checkpoint.load_splats(self, splats)
 
-    def save_ply(self, path, sh_degree: Optional[int] = None):
+    def save_ply(self, path, sh_degree: Optional[int] = None, transform=None):
         """simple_trainer.py save_ply / ply_steps (:748-765): gsplat_hip.save_ply
         of the synced parameters; app_opt: the colours baked at the zero
         embedding and zero view direction at `sh_degree` (the reference passes
-        the step's sh_degree_to_use; None: the trainer's sh_degree)."""
+        the step's sh_degree_to_use; None: the trainer's sh_degree).
+
+        `transform` ([4,4] similarity, numpy or tensor): the parameters go
+        through `gsplat_hip.transform_splats` first, so the file is written in
+        another frame; `transform=np.linalg.inv(parser.transform)` gives
+        COLMAP's frame for a scene trained on `colmap.Parser(normalize=True)`.
+        With app_opt the baked colours do not depend on the view, so only the
+        geometry moves.  None: the bytes written are those of the parameters
+        as they are."""
         from . import checkpoint
-        return checkpoint.save_ply(self, path, sh_degree)
+        return checkpoint.save_ply(self, path, sh_degree, transform)
 
     # ------------------------------------------------------------ strategy
     def post_step(self, it: int, replayed: bool = False):

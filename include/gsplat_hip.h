@@ -72,7 +72,9 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_tsdf_integrate, gsplat_hip_mc_count / _emit / _table /
  *     _workspace_bytes (mesh export);
  *     gsplat_hip_color_correct and gsplat_hip_color_correct_workspace_bytes
- *     (colour-corrected evaluation). */
+ *     (colour-corrected evaluation);
+ *     gsplat_hip_splat_xform_record_floats / _prepare / _apply / _rotate_sh
+ *     (similarity transforms of splat scenes). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1527,6 +1529,50 @@ int64_t gsplat_hip_color_correct_workspace_bytes(int64_t P);
 int gsplat_hip_color_correct(int64_t P, const float *img, const float *ref, int num_iters,
                              double eps, float *out, void *workspace, int32_t *fallbacks,
                              void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Similarity transforms of splat scenes (ABI 38, new entries only;
+ * csrc/transform.hip; no reference counterpart).  Per segment x' = A x + t
+ * with A = s R, s > 0, R a proper rotation:
+ *   means' = A means + t, quats' = q_R (x) quats (wxyz, not renormalised),
+ *   scales' = scales + log s, and per degree l = 1..degree and colour channel
+ *   the 2l+1 coefficients of shN times M_l(R), where
+ *   sum_k a'_k Y_k(d) = sum_k a_k Y_k(R^T d) in the basis of csrc/sh_basis.h.
+ *
+ *   _record_floats(degree): floats per segment record, 20 + {0, 9, 34, 83,
+ *     164}[degree]; 0 for a degree outside [0, 4].
+ *   _prepare: transforms [S,4,4] float64 row-major on the device (the fourth
+ *     row is not read) -> records [S, record_floats] float32 (A[9], t[3],
+ *     q_R[4], log s, s, 2 unused, then M_1..M_degree row-major), computed in
+ *     float64, and status [S] int32: bit 0 for det A <= 0, bit 1 for
+ *     max|A^T A / s^2 - I| > 1e-4 (or a non-finite entry).
+ *   _apply: N Gaussians; segment_ids int64 [N] or null (every row uses segment
+ *     0).  means [N,3], quats [N,4], scales [N,3], shN [N, (degree+1)^2 - 1, 3]
+ *     float32, contiguous, 16-B aligned; shN and out_shN may be null at degree
+ *     0.  Each output is its input itself (in place) or does not overlap it.
+ *     A row whose id is outside [0, S) or whose segment has a nonzero status
+ *     is copied through; no record out of range is read.  counter: one int64,
+ *     8-B aligned, zeroed by a kernel and then set to the number of ids
+ *     outside [0, S): the kernel's only atomic, one integer add per wave that
+ *     holds such an id (none when every id is in range).  The data path has
+ *     no atomics: the same bits on every run.
+ *   _rotate_sh: the shN part of _apply alone, degree >= 1.
+ * All launch on `stream`, allocate nothing and never synchronise.  Status 1
+ * with a message for a null pointer other than those named above, a
+ * misaligned or partly overlapping buffer, or a size out of range. */
+int gsplat_hip_splat_xform_record_floats(int degree);
+int gsplat_hip_splat_xform_prepare(int64_t S, int degree, const double *transforms,
+                                   float *records, int32_t *status, void *stream);
+int gsplat_hip_splat_xform_apply(int64_t N, int degree, int64_t S, const float *records,
+                                 const int32_t *status, const int64_t *segment_ids,
+                                 const float *means, const float *quats, const float *scales,
+                                 const float *shN, float *out_means, float *out_quats,
+                                 float *out_scales, float *out_shN, int64_t *counter,
+                                 void *stream);
+int gsplat_hip_splat_xform_rotate_sh(int64_t N, int degree, int64_t S, const float *records,
+                                     const int32_t *status, const int64_t *segment_ids,
+                                     const float *shN, float *out_shN, int64_t *counter,
+                                     void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
