@@ -26,6 +26,7 @@ from .appearance import appearance_colors
 from .bilagrid import bilagrid_identity, bilagrid_lr, bilagrid_slice, bilagrid_tv_loss
 from .color_correct import color_correct
 from .compression import PngCompression
+from .contributions import contribution_scores, prune_splats, rasterize_to_contributions
 from .depth_loss import sparse_depth_loss
 from .io import load_ply, save_ply
 from .losses import geometry_loss_2dgs
@@ -76,5 +77,8 @@ __all__ = [
     "rotate_sh",
     "sh_rotation_matrices",
     "merge_splats",
+    "rasterize_to_contributions",
+    "contribution_scores",
+    "prune_splats",
 ]
 __version__ = "0.1.0"

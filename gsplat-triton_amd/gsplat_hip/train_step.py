@@ -271,6 +271,8 @@ _REFUSALS = {
     "compression": ("one-GPU trainers only", _MANY),
     "checkpoint": ("one-GPU trainers only", _MANY),
     "mesh": ("one-GPU trainers only", _MANY),
+    "scores": ("one-GPU 3DGS trainers without app_opt only",
+               ("model='2dgs'", "app_opt") + _MANY),
 }
 
 
@@ -1499,6 +1501,29 @@ class Trainer:
         if path is not None:
             save_mesh_ply(path, *mesh)
         return mesh
+
+    # -------------------------------------------------- contribution scores
+    @torch.no_grad()
+    def contribution_scores(self, pixel_weights=None, camera_batch=8):
+        """{"sum", "max", "count"}, each [N]: every Gaussian's blending weight
+        alpha * T summed (times `pixel_weights` [n_cameras, H, W] when given)
+        and maximised over all pixels of the training cameras, and the number
+        of pixels that blended it (contributions.contribution_scores, from the
+        activated parameters).  What contribution-based pruning ranks by; the
+        parameters, the optimizer state and a captured step are not touched."""
+        name = "contribution_scores"
+        _refuse("scores", {"model='2dgs'": self.model == "2dgs", "app_opt": self.app_opt,
+                           "gaussian_shard": self.gshard,
+                           "sharded_optimizer": bool(self.sharded),
+                           "world_size": self.world_size != 1}, name=name)
+        from .contributions import contribution_scores
+        self.sync()
+        p = {k: v.detach() for k, v in self.params.items()}
+        return contribution_scores(
+            p["means"], p["quats"], torch.exp(p["scales"]), torch.sigmoid(p["opacities"]),
+            self.viewmats, self.Ks, self.width, self.height, camera_batch=camera_batch,
+            pixel_weights=pixel_weights, near_plane=0.01, far_plane=1e10,
+            rasterize_mode=self.rasterize_mode)
 
     # ---------------------------------------------------------- persistence
     def save_checkpoint(self, path, step: int):

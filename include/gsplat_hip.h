@@ -74,7 +74,8 @@ const char *gsplat_hip_last_error(void);
  *     gsplat_hip_color_correct and gsplat_hip_color_correct_workspace_bytes
  *     (colour-corrected evaluation);
  *     gsplat_hip_splat_xform_record_floats / _prepare / _apply / _rotate_sh
- *     (similarity transforms of splat scenes). */
+ *     (similarity transforms of splat scenes);
+ *     gsplat_hip_rasterize_score (per-Gaussian contribution scores). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1084,6 +1085,30 @@ int gsplat_hip_rasterize_to_indices_write(int kind, int C, int N, int W, int H, 
                                           const int32_t *offsets, const int32_t *flatten_ids,
                                           const int32_t *chunk_starts, int64_t *gaussian_ids,
                                           int64_t *pixel_ids, void *stream);
+
+/* Per-Gaussian contribution scores (csrc/rasterize_score.hip): the 16x16
+ * forward's walk over the tiles' records, reduced over the pixels per
+ * Gaussian.  Inputs as gsplat_hip_rasterize_fwd without colours and
+ * backgrounds: means2d[G,2], conics[G,3], opacities[G] with G = C*N (dense)
+ * or nnz (packed), offsets[C,th,tw], flatten_ids[n_isects] indexing those
+ * rows; masks (may be NULL; u8[C,th,tw], non-zero skips the tile as in the
+ * forward); pixel_weights (may be NULL; f32[C,H,W]).  With w = alpha * T of a
+ * (pixel, record) pair that the forward blends, row r receives
+ *   sum[r]   += w * pixel_weights[pixel]   (float atomics: the order of the
+ *               tiles' additions, and with it the last bits, varies by run),
+ *   max[r]    = max(max[r], w)             (unweighted; same bits every run),
+ *   count[r] += 1                          (same bits every run),
+ * where r = flatten id, or flatten id % N with fold != 0 (dense only: the
+ * cameras' rows of one Gaussian fold into one).  n_rows = rows of sum / max /
+ * count; accumulate == 0 zero-fills them first, != 0 adds to their contents.
+ * tile_size must be 16.  Forward only. */
+int gsplat_hip_rasterize_score(int C, int N, int64_t n_rows, int W, int H, int tile_size,
+                               int tile_width, int tile_height, const float *means2d,
+                               const float *conics, const float *opacities,
+                               const uint8_t *masks, const float *pixel_weights,
+                               const int32_t *offsets, int64_t n_isects,
+                               const int32_t *flatten_ids, int fold, int accumulate, float *sum,
+                               float *max, int32_t *count, void *stream);
 
 /* Normals from depth maps (gsplat/utils.py:201-224, depth_to_normal, called by
  * rasterization_2dgs for render_normals_from_depth): depths[C,H,W] (the [..,1]
