@@ -184,6 +184,10 @@ _SIGS = {
                                                      _p, _p, _p, _p, _p]),
     "gsplat_hip_rasterize_score": (_i32, [_i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p,
                                           _p, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p]),
+    "gsplat_hip_rasterize_wide_supported": (_i32, [_i32, _i32]),
+    "gsplat_hip_rasterize_wide_fwd": (_i32, [_i32] * 7 + [_p] * 7 + [_i64] + [_p] * 5),
+    "gsplat_hip_rasterize_wide_bwd": (_i32, [_i32, _i64] + [_i32] * 6 + [_p] * 7 + [_i64]
+                                      + [_p] * 11),
     "gsplat_hip_depth_to_normal": (_i32, [_i32, _i32, _i32, _p, _i64, _p, _p, _i32, _p, _p]),
     "gsplat_hip_rotate3": (_i32, [_i32, _i64, _p, _p, _p, _p]),
     "gsplat_hip_geom_loss_2dgs_workspace_bytes": (_i64, [_i32, _i32, _i32]),

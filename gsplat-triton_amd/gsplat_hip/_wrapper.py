@@ -1076,6 +1076,71 @@ class _RasterizeToPixels(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None, None, None, None)
 
 
+class _RasterizeToPixelsWide(torch.autograd.Function):
+    """_RasterizeToPixels for more than 32 channels and 16x16 tiles
+    (csrc/rasterize_wide.hip): one forward and one backward launch for all
+    channels, the blend on the matrix cores."""
+
+    @staticmethod
+    def forward(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
+                tile_size, isect_offsets, flatten_ids, absgrad):
+        ctx.means2d_in = means2d if absgrad else None  # receives .absgrad
+        ctx.set_materialize_grads(False)  # alphas without a loss: None, not zeros
+        means2d, conics, colors, opacities, backgrounds = (
+            _f32c(x) for x in (means2d, conics, colors, opacities, backgrounds))
+        _dev_check(means2d, conics, colors, opacities, isect_offsets, flatten_ids)
+        isect_offsets = isect_offsets.to(torch.int32).contiguous()
+        flatten_ids = flatten_ids.to(torch.int32).contiguous()
+        m = None if masks is None else masks.to(torch.bool).contiguous()
+        C, th, tw = isect_offsets.shape
+        D = colors.shape[-1]
+        dev = means2d.device
+        render_colors = torch.empty((C, height, width, D), device=dev)
+        render_alphas = torch.empty((C, height, width, 1), device=dev)
+        last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev)
+        with _Timed("rasterize_wide_fwd"):
+            _lib.call("gsplat_hip_rasterize_wide_fwd", C, D, width, height, tile_size, tw, th,
+                      _ptr(means2d), _ptr(conics), _ptr(colors), _ptr(opacities),
+                      _ptr(backgrounds), _ptr(m), _ptr(isect_offsets), flatten_ids.numel(),
+                      _ptr(flatten_ids), _ptr(render_colors), _ptr(render_alphas),
+                      _ptr(last_ids), _stream())
+        ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, m, isect_offsets,
+                              flatten_ids, render_alphas, last_ids)
+        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad = width, height, tile_size, absgrad
+        return render_colors, render_alphas
+
+    @staticmethod
+    def backward(ctx, v_render_colors, v_render_alphas):
+        (means2d, conics, colors, opacities, backgrounds, m, isect_offsets, flatten_ids,
+         render_alphas, last_ids) = ctx.saved_tensors
+        C, th, tw = isect_offsets.shape
+        D = colors.shape[-1]
+        if v_render_colors is None:
+            v_render_colors = torch.zeros((C, ctx.height, ctx.width, D), device=means2d.device)
+        v_render_colors = _f32c(v_render_colors)
+        v_render_alphas = _f32c(v_render_alphas)  # None: alphas unused (null in the ABI)
+        v_means2d = torch.empty_like(means2d)
+        v_conics = torch.empty_like(conics)
+        v_colors = torch.empty_like(colors)
+        v_opacities = torch.empty_like(opacities)
+        v_abs = torch.empty_like(means2d) if ctx.absgrad else None
+        with _Timed("rasterize_wide_bwd"):
+            _lib.call("gsplat_hip_rasterize_wide_bwd", C, opacities.numel(), D, ctx.width,
+                      ctx.height, ctx.tile_size, tw, th, _ptr(means2d), _ptr(conics),
+                      _ptr(colors), _ptr(opacities), _ptr(backgrounds), _ptr(m),
+                      _ptr(isect_offsets), flatten_ids.numel(), _ptr(flatten_ids),
+                      _ptr(render_alphas), _ptr(last_ids), _ptr(v_render_colors),
+                      _ptr(v_render_alphas), _ptr(v_means2d), _ptr(v_conics), _ptr(v_colors),
+                      _ptr(v_opacities), _ptr(v_abs), _stream())
+        if ctx.absgrad:
+            ctx.means2d_in.absgrad = v_abs
+        v_backgrounds = None
+        if ctx.needs_input_grad[4]:
+            v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
+        return (v_means2d, v_conics, v_colors, v_opacities, v_backgrounds,
+                None, None, None, None, None, None, None)
+
+
 def rasterize_to_pixels(
     means2d: Tensor,  # [C, N, 2] or [nnz, 2]
     conics: Tensor,  # [C, N, 3] or [nnz, 3]
@@ -1091,15 +1156,18 @@ def rasterize_to_pixels(
     packed: bool = False,
     absgrad: bool = False,
     block_size: int = 8,
+    wide: bool = False,
 ) -> Tuple[Tensor, Tensor]:
     """Rasterizes Gaussians to pixels (_wrapper.py:185-297).
 
     Returns render_colors [C,H,W,channels] and render_alphas [C,H,W,1].
     Channel counts outside {1,2,3,4,8,16,32} are zero-padded to the next one;
-    above 32 they are rendered in chunks of 32."""
+    above 32 they are rendered in chunks of 32, or with `wide=True` (16x16
+    tiles) by the wide-channel kernels in one forward and one backward launch
+    (csrc/rasterize_wide.hip: the blend on the matrix cores)."""
     return _rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_height,
                                 tile_size, isect_offsets, flatten_ids, backgrounds, masks, packed,
-                                absgrad, block_size)
+                                absgrad, block_size, wide=wide)
 
 
 @contextlib.contextmanager
@@ -1190,12 +1258,14 @@ def pack_render_records(means2d, conics, colors, opacities, tile_size, visible=N
 def _rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_height, tile_size,
                          isect_offsets, flatten_ids, backgrounds=None, masks=None, packed=False,
                          absgrad=False, block_size=8, visible=None, records=None,
-                         n_isects_device=None, ranks=None):
+                         n_isects_device=None, ranks=None, wide=False):
     """rasterize_to_pixels with rasterization()'s private hints: `visible`
     ([C,N] tiles_per_gauss: only those Gaussians' render records are packed)
     and `records` (already packed by pack_render_records for these exact
     colours; used when no channel padding or chunking applies), and
-    `n_isects_device` (flatten_ids is a capacity-sized array, finish_capped)."""
+    `n_isects_device` (flatten_ids is a capacity-sized array, finish_capped).
+    `wide`: more than 32 channels go to _RasterizeToPixelsWide (`flatten_ids`
+    are then Gaussian ids, never ranks)."""
     if n_isects_device is not None:
         assert tile_size == 16, "a device isect count needs 16x16 tiles"
     C = isect_offsets.size(0)
@@ -1240,6 +1310,16 @@ def _rasterize_to_pixels(means2d, conics, colors, opacities, image_width, image_
                                           n_isects_device, ranks)
         return (rc[..., :D] if Dp != D else rc), ra
 
+    if wide and channels > 32:
+        if tile_size != 16:
+            raise NotImplementedError(f"wide=True with tile_size={tile_size} is not supported: "
+                                      "the wide-channel kernels render 16x16 tiles")
+        if n_isects_device is not None:
+            raise NotImplementedError("wide=True with a device isect count is not supported: "
+                                      "the wide-channel kernels take n_isects from the host")
+        return _RasterizeToPixelsWide.apply(
+            means2d, conics, colors, opacities, backgrounds, masks, image_width, image_height,
+            tile_size, isect_offsets, flatten_ids, absgrad)
     if channels <= 32:
         render_colors, render_alphas = run(colors, backgrounds)
     else:

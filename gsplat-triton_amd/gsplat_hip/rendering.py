@@ -73,6 +73,7 @@ def rasterization(
     distributed: bool = False,
     camera_model: str = "pinhole",
     covars: Optional[Tensor] = None,
+    wide_channels: bool = False,
     _colors_ready: Optional[Callable[[], None]] = None,
     _fusion=None,
     _isect_capacity: Optional[int] = None,
@@ -90,6 +91,11 @@ def rasterization(
     triangle goes to the projection from covariances
     (csrc/projection_covar.hip); everything after it is unchanged.  Not with
     distributed=True.
+
+    `wide_channels`: more than 32 rasterized channels (feature fields; the
+    depth channel of RGB+D / RGB+ED counts) go to the wide-channel kernels
+    (csrc/rasterize_wide.hip) in one forward and one backward launch instead
+    of `channel_chunk`-sized renders; 16x16 tiles, not with `_isect_capacity`.
 
     Private arguments of the training harness (train_step.Trainer):
     `_colors_ready` (see below) and `_fusion`, a _wrapper.StepFusion handed
@@ -129,6 +135,10 @@ def rasterization(
         quats, scales = None, None  # ignored (gsplat/rendering.py:246-254)
         tri_indices = ([0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2])
         covars = covars[..., tri_indices[0], tri_indices[1]]  # [N, 6]
+    if wide_channels and (distributed or _isect_capacity is not None):
+        raise NotImplementedError("wide_channels=True is not supported with distributed=True or "
+                                  "the sync-free tile intersection: the wide-channel kernels "
+                                  "render one rank's Gaussians with n_isects on the host")
     assert opacities.shape == (N,), opacities.shape
     assert viewmats.shape == (C, 4, 4), viewmats.shape
     assert Ks.shape == (C, 3, 3), Ks.shape
@@ -367,7 +377,12 @@ def rasterization(
 
     # only Gaussians with a tile are gathered: pack just their render records
     visible = None if packed else tiles_per_gauss
-    if colors.shape[-1] > channel_chunk:
+    if wide_channels and colors.shape[-1] > 32:
+        render_colors, render_alphas = _rasterize_to_pixels(
+            means2d, conics, colors, opacities, width, height, tile_size, isect_offsets,
+            flatten_ids, backgrounds=backgrounds, packed=packed, absgrad=absgrad,
+            n_isects_device=counts, wide=True)
+    elif colors.shape[-1] > channel_chunk:
         n_chunks = (colors.shape[-1] + channel_chunk - 1) // channel_chunk
         render_colors, render_alphas = [], []
         for i in range(n_chunks):

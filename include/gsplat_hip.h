@@ -75,7 +75,9 @@ const char *gsplat_hip_last_error(void);
  *     (colour-corrected evaluation);
  *     gsplat_hip_splat_xform_record_floats / _prepare / _apply / _rotate_sh
  *     (similarity transforms of splat scenes);
- *     gsplat_hip_rasterize_score (per-Gaussian contribution scores). */
+ *     gsplat_hip_rasterize_score (per-Gaussian contribution scores);
+ *     gsplat_hip_rasterize_wide_supported / _fwd / _bwd (the wide-channel
+ *     rasterizer: 33..512 channels blended on the matrix cores). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1109,6 +1111,35 @@ int gsplat_hip_rasterize_score(int C, int N, int64_t n_rows, int W, int H, int t
                                const int32_t *offsets, int64_t n_isects,
                                const int32_t *flatten_ids, int fold, int accumulate, float *sum,
                                float *max, int32_t *count, void *stream);
+
+/* Wide-channel rasterizer (csrc/rasterize_wide.hip): rasterize_to_pixels for
+ * 33 <= D <= 512 colour channels and 16x16 tiles in one forward and one
+ * backward launch, the blend and both colour products of the backward on the
+ * matrix cores (v_mfma_f32_32x32x2_f32 / _16x16x4_f32, fp32 inputs).  Arguments
+ * and semantics as gsplat_hip_rasterize_fwd / _bwd (any D in the range: no
+ * padding by the caller), without render records, state, workspace and a
+ * device isect count.  _supported: 1 if (D, tile_size) has these kernels.
+ * The backward zero-fills its five outputs first (v_means2d_abs may be NULL);
+ * v_render_alphas may be NULL. */
+int gsplat_hip_rasterize_wide_supported(int D, int tile_size);
+int gsplat_hip_rasterize_wide_fwd(int C, int D, int width, int height, int tile_size,
+                                  int tile_width, int tile_height, const float *means2d,
+                                  const float *conics, const float *colors,
+                                  const float *opacities, const float *backgrounds,
+                                  const uint8_t *masks, const int32_t *isect_offsets,
+                                  int64_t n_isects, const int32_t *flatten_ids,
+                                  float *render_colors, float *render_alphas, int32_t *last_ids,
+                                  void *stream);
+int gsplat_hip_rasterize_wide_bwd(int C, int64_t n_gaussians, int D, int width, int height,
+                                  int tile_size, int tile_width, int tile_height,
+                                  const float *means2d, const float *conics, const float *colors,
+                                  const float *opacities, const float *backgrounds,
+                                  const uint8_t *masks, const int32_t *isect_offsets,
+                                  int64_t n_isects, const int32_t *flatten_ids,
+                                  const float *render_alphas, const int32_t *last_ids,
+                                  const float *v_render_colors, const float *v_render_alphas,
+                                  float *v_means2d, float *v_conics, float *v_colors,
+                                  float *v_opacities, float *v_means2d_abs, void *stream);
 
 /* Normals from depth maps (gsplat/utils.py:201-224, depth_to_normal, called by
  * rasterization_2dgs for render_normals_from_depth): depths[C,H,W] (the [..,1]
