@@ -21,14 +21,12 @@
 // read back as LDS broadcasts.  This is a debug / playground path (the
 // reference's `_rasterize_to_pixels` + `accumulate`), so it favours a plain
 // layout over the wave-per-strip machinery of the training rasterizers.
-#include "common.h"
+#include "raster_tile.h"
 #include "../../include/gsplat_hip.h"
 
 namespace idxk {
 
-constexpr float kAlphaMin = 1.f / 255.f;
-constexpr float kAlphaMax = 0.999f;
-constexpr float kTMin = 1e-4f;
+using gs::kAlphaMax, gs::kAlphaMin, gs::kTMin;  // raster_tile.h
 constexpr float kFilterInvSquare = 2.f;  // FILTER_INV_SQUARE_2DGS, Rasterization.h:11
 constexpr int kMaxLanes = 1024;
 

@@ -3,7 +3,7 @@
 // side (rasterize16.hip) asks of the planning side (rasterize16_plan.hip).
 #pragma once
 
-#include "common.h"
+#include "raster_tile.h"
 
 // Colour channel counts with compiled forward and backward kernels, for every
 // tile size (the caller pads others).
@@ -43,9 +43,7 @@ int64_t rasterize16_bwd_workspace(int64_t G, int D, bool absgrad, int n_tiles, i
 namespace r16 {
 
 constexpr int kTS = 16;
-constexpr float kAlphaMin = 1.f / 255.f;
-constexpr float kAlphaMax = 0.999f;
-constexpr float kTMin = 1e-4f;
+using gs::kAlphaMax, gs::kAlphaMin, gs::kTMin, gs::isect_count, gs::tile_end;  // raster_tile.h
 
 // Render records: one 64-B row per Gaussian, [x, y, a, b, c, opacity,
 // colour[D], pad] (D <= kRecMaxD), so the per-isect gather of a batch touches
@@ -98,14 +96,7 @@ struct Args {
   uint64_t *timeline;  // debug: per-wave (start, end) s_memrealtime stamps or null
 };
 
-// Isect count and the end of tile t's isect range.  Capacity mode (n_dev
-// non-null, the sync-free isect of a captured training step): the arrays
-// hold n_isects slots, the count is read on the device.
-GS_INLINE int64_t isect_count(const int64_t *n_dev, int64_t n) { return n_dev ? *n_dev : n; }
-GS_INLINE int64_t tile_end(const int32_t *offsets, int t, int n_tiles, const int64_t *n_dev,
-                           int64_t n) {
-  return t == n_tiles - 1 ? isect_count(n_dev, n) : (int64_t)offsets[t + 1];
-}
+// The end of tile t's isect range (raster_tile.h's tile_end of these args).
 GS_INLINE int64_t tile_end(const Args &a, int t) {
   return tile_end(a.offsets, t, a.n_tiles, a.n_dev, a.n_isects);
 }

@@ -30,7 +30,7 @@
 //           blended the record.
 // A wave whose pixels have all terminated skips walk and reduce (it still
 // helps staging, which is shared); the workgroup leaves when all four have.
-#include "common.h"
+#include "raster_tile.h"
 #include "wave_ops.h"
 
 #include "../../include/gsplat_hip.h"
@@ -41,9 +41,6 @@ namespace score {
 constexpr int kTS = 16;
 constexpr int kBatch = 64;
 constexpr int kGroup = 16;  // records per reduce-scatter
-constexpr float kAlphaMin = 1.f / 255.f;
-constexpr float kAlphaMax = 0.999f;
-constexpr float kTMin = 1e-4f;
 constexpr float kLog2e = 1.4426950408889634f;
 
 struct Args {
@@ -55,49 +52,6 @@ struct Args {
   float *sum, *max;
   int32_t *count;
 };
-
-// ---- the max twin of wave_ops.h's reduce_scatter (same lane pairing, so
-// rs_field() names the field of both)
-GS_INLINE float swap32_max(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-GS_INLINE float swap16_max(float a, float b) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-// s_nop 1: the VALU-write -> DPP-read hazard (see add_b3)
-GS_INLINE float max_b3(float lo, float hi) {
-  float r;
-  asm("s_nop 1\n\t"
-      "v_max_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_max_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc"
-      : "=&v"(r)
-      : "v"(lo), "v"(hi));
-  return r;
-}
-GS_INLINE float max_b2(float lo, float hi) {
-  float r;
-  asm("s_nop 1\n\t"
-      "v_max_f32_dpp %0, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
-      "v_max_f32_dpp %0, %2, %2 row_ror:4 row_mask:0xf bank_mask:0xa"
-      : "=&v"(r)
-      : "v"(lo), "v"(hi));
-  return r;
-}
-GS_INLINE float reduce_scatter_max16(const float *v) {
-  float w[8], x[4], y[2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = swap32_max(v[2 * i], v[2 * i + 1]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = swap16_max(w[2 * i], w[2 * i + 1]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) y[i] = max_b3(x[2 * i], x[2 * i + 1]);
-  float z = max_b2(y[0], y[1]);
-  z = fmaxf(z, dpp<0xB1>(z));  // quad lane ^ 1
-  z = fmaxf(z, dpp<0x4E>(z));  // quad lane ^ 2
-  return z;
-}
 
 __global__ void __launch_bounds__(256) score_kernel(const Args a) {
   // staged records, double-buffered: batch b + 1 is staged while a slower
@@ -183,7 +137,7 @@ __global__ void __launch_bounds__(256) score_kernel(const Args a) {
           T = blend ? nT : (hit ? -fabsf(T) : T);
         }
         const float zs = reduce_scatter<kGroup>(ws, lane);
-        const float zm = reduce_scatter_max16(w);
+        const float zm = reduce_scatter<kGroup, Max>(w, lane);
         const float zc = reduce_scatter<kGroup>(wc, lane);
         if ((lane & 3) == grp) ms = zs, mm = zm, mc = zc;
       }

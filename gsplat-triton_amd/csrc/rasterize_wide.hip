@@ -40,6 +40,9 @@
 // v_alpha is linear in q, so the slabs add their geometry gradients
 // independently; the render-alpha cotangent belongs to slab 0.  Channels past
 // D inside the last slab are staged as zeros and never stored.
+//
+// The argument block, the tile and pixel walk, the geometry staging and the
+// per-record alpha steps are raster_tile.h's, shared with rasterize.hip.
 #include "raster16.h"
 #include "wave_ops.h"
 #include "../../include/gsplat_hip.h"
@@ -50,10 +53,6 @@ namespace wide {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-using r16::kAlphaMax;
-using r16::kAlphaMin;
-using r16::kTMin;
-
 constexpr int kMinD = 33, kMaxD = 512;
 constexpr int kBatch = 32;     // Gaussians per staged batch
 constexpr int kFwdSlab = 128;  // forward: channels per workgroup (4 MFMA column blocks)
@@ -63,67 +62,19 @@ constexpr int kBwdSlab = 64;   // backward: channels per workgroup (v_out fits L
 constexpr int kBwdLd = kBwdSlab + 4;  // v_out [256][.], colours [kBatch][.]
 constexpr int kWLd = 256 + 4;         // q / w [kBatch][.]
 
-struct Args {
-  int C, D, W, H, tw, th, n_tiles;
-  int64_t n_isects;
-  const float *means2d, *conics, *colors, *opacities, *backgrounds;  // backgrounds nullable
-  const uint8_t *masks;                                              // nullable
-  const int32_t *offsets, *flatten_ids;
-  float *render_colors, *render_alphas;
-  int32_t *last_ids;
-  const float *v_render_colors, *v_render_alphas;  // alphas nullable
-  float *v_means2d, *v_conics, *v_colors, *v_opacities, *v_abs;  // abs nullable
-};
-
-struct Geom {
-  float2 xy[kBatch];
-  float4 con[kBatch];  // conic a, b, c, opacity
-  int32_t gid[kBatch];
-};
-
-struct Tile {
-  int tile, slab, c, x0, y0;
-  int64_t start, end;
-};
-
-GS_INLINE Tile tile_of(const Args &a, int nslab) {
-  Tile t;
-  t.tile = blockIdx.x / nslab;
-  t.slab = blockIdx.x - t.tile * nslab;
-  const int per = a.tw * a.th;
-  t.c = t.tile / per;
-  const int rem = t.tile - t.c * per;
-  const int ty = rem / a.tw;
-  t.x0 = (rem - ty * a.tw) * r16::kTS;
-  t.y0 = ty * r16::kTS;
-  t.start = a.offsets[t.tile];
-  t.end = r16::tile_end(a.offsets, t.tile, a.n_tiles, nullptr, a.n_isects);
-  return t;
-}
-
 // Pixel p (0..255, row-major in the tile; wave w owns 64 w ..) of the tile:
 // its index into the [C,H,W] images, or -1 outside the image.
-GS_INLINE int64_t pixel_index(const Args &a, const Tile &t, int p) {
-  const int x = t.x0 + (p & 15), y = t.y0 + (p >> 4);
-  return (x < a.W && y < a.H) ? ((int64_t)t.c * a.H + y) * a.W + x : -1;
-}
-
-GS_INLINE void stage_geom(const Args &a, Geom &s, int64_t b0, int nb) {
-  const int j = threadIdx.x;
-  if (j < nb) {
-    const int32_t g = a.flatten_ids[b0 + j];
-    s.gid[j] = g;
-    s.xy[j] = *reinterpret_cast<const float2 *>(a.means2d + 2 * (int64_t)g);
-    const float *cn = a.conics + 3 * (int64_t)g;
-    s.con[j] = make_float4(cn[0], cn[1], cn[2], a.opacities[g]);
-  }
+GS_INLINE int64_t pixel_index(const TileArgs &a, const TileCtx &t, int p) {
+  const TilePixel px = tile_pixel(t, r16::kTS, p);
+  return in_image(a, px) ? image_index(a, t, px) : -1;
 }
 
 // Rows b0 .. b0 + nb of the slab's colours into s_col[row][LD]: NC (a power of
 // two) columns from channel ch0, zeros past D; with ZERO_ROWS the rows from nb
 // to kBatch are zeroed too (they enter a product).
 template <int NC, int LD, bool ZERO_ROWS>
-GS_INLINE void stage_colors(const Args &a, float *s_col, int64_t b0, int nb, int ch0, int ncols) {
+GS_INLINE void stage_colors(const TileArgs &a, float *s_col, int64_t b0, int nb, int ch0,
+                            int ncols) {
   const int col = threadIdx.x & (NC - 1);
   const int ch = ch0 + col;
   if (col >= ncols) return;
@@ -135,18 +86,20 @@ GS_INLINE void stage_colors(const Args &a, float *s_col, int64_t b0, int nb, int
 }
 
 // ------------------------------------------------------------------ forward
-__global__ void __launch_bounds__(256, 2) wide_fwd_kernel(Args a, int nslab) {
-  __shared__ Geom s;
+__global__ void __launch_bounds__(256, 2) wide_fwd_kernel(TileArgs a, int nslab) {
+  __shared__ Geom<kBatch> s;
   __shared__ float s_col[kBatch * kFwdSlab];
   __shared__ float s_w[4][kBatch * 64];  // per wave: w[Gaussian][pixel]
   __shared__ float s_T[4][64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int i = lane & 31, h = lane >> 5;
-  const Tile t = tile_of(a, nslab);
-  const int ch0 = t.slab * kFwdSlab;
+  // workgroup = (tile, slab): blockIdx.x = tile * nslab + slab
+  const int tile = blockIdx.x / nslab, slab = blockIdx.x - tile * nslab;
+  const TileCtx t = tile_ctx(a, tile, r16::kTS, a.n_tiles);
+  const int ch0 = slab * kFwdSlab;
   const int nblk = min(4, (a.D - ch0 + 31) / 32);  // 32-channel blocks in use
+  const TilePixel px = tile_pixel(t, r16::kTS, tid);
   const int64_t pix = pixel_index(a, t, tid);
-  const float fx = (float)(t.x0 + (tid & 15)) + 0.5f, fy = (float)(t.y0 + (tid >> 4)) + 0.5f;
 
   f32x16 acc[2][4];
 #pragma unroll
@@ -178,17 +131,13 @@ __global__ void __launch_bounds__(256, 2) wide_fwd_kernel(Args a, int nslab) {
         for (int k = 0; k < nb; ++k) {
           float w = 0.f;
           if (!done) {
-            const float2 xy = s.xy[k];
-            const float4 cn = s.con[k];
-            const float dx = xy.x - fx, dy = xy.y - fy;
-            const float sigma = 0.5f * (cn.x * dx * dx + cn.z * dy * dy) + cn.y * dx * dy;
-            const float alpha = fminf(kAlphaMax, cn.w * __expf(-sigma));
-            if (sigma >= 0.f && alpha >= kAlphaMin) {
-              const float next_T = T * (1.f - alpha);
+            const FwdRecord r = fwd_record(s.xy[k], s.con[k], px.fx, px.fy);
+            if (blends(r)) {
+              const float next_T = T * (1.f - r.alpha);
               if (next_T <= kTMin) {
                 done = true;
               } else {
-                w = alpha * T;
+                w = r.alpha * T;
                 T = next_T;
                 last = (int32_t)(b0 + k);
               }
@@ -226,7 +175,7 @@ __global__ void __launch_bounds__(256, 2) wide_fwd_kernel(Args a, int nslab) {
     }
   }
 
-  if (t.slab == 0 && pix >= 0) {
+  if (slab == 0 && pix >= 0) {
     a.render_alphas[pix] = 1.f - T;
     a.last_ids[pix] = last;
   }
@@ -259,8 +208,8 @@ __global__ void __launch_bounds__(256, 2) wide_fwd_kernel(Args a, int nslab) {
 
 // ----------------------------------------------------------------- backward
 template <bool ABS>
-__global__ void __launch_bounds__(256) wide_bwd_kernel(Args a, int nslab) {
-  __shared__ Geom s;
+__global__ void __launch_bounds__(256) wide_bwd_kernel(TileArgs a, int nslab) {
+  __shared__ Geom<kBatch> s;
   __shared__ float s_vout[256 * kBwdLd];  // v_out[pixel][channel] of the tile and slab
   __shared__ float s_col[kBatch * kBwdLd];
   __shared__ float s_qw[kBatch * kWLd];  // q, then w, [Gaussian][pixel]
@@ -268,13 +217,15 @@ __global__ void __launch_bounds__(256) wide_bwd_kernel(Args a, int nslab) {
   __shared__ int32_t s_maxlast[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int i = lane & 15, j = lane >> 4;
-  const Tile t = tile_of(a, nslab);
+  // workgroup = (tile, slab): blockIdx.x = tile * nslab + slab
+  const int tile = blockIdx.x / nslab, slab = blockIdx.x - tile * nslab;
+  const TileCtx t = tile_ctx(a, tile, r16::kTS, a.n_tiles);
   if (a.masks && a.masks[t.tile]) return;
-  const int ch0 = t.slab * kBwdSlab;
+  const int ch0 = slab * kBwdSlab;
   const int nch = min(kBwdSlab, a.D - ch0);
   const int ksteps = (nch + 3) / 4;
+  const TilePixel px = tile_pixel(t, r16::kTS, tid);
   const int64_t pix = pixel_index(a, t, tid);
-  const float fx = (float)(t.x0 + (tid & 15)) + 0.5f, fy = (float)(t.y0 + (tid >> 4)) + 0.5f;
 
   // v_out of the tile, zeros outside the image and past D
   {
@@ -291,16 +242,10 @@ __global__ void __launch_bounds__(256) wide_bwd_kernel(Args a, int nslab) {
   int32_t my_last = -1;
   if (pix >= 0) {
     T_final = 1.f - a.render_alphas[pix];
-    if (t.slab == 0 && a.v_render_alphas) Dra = a.v_render_alphas[pix];
+    if (slab == 0 && a.v_render_alphas) Dra = a.v_render_alphas[pix];
     my_last = a.last_ids[pix];
   }
-  // truncate the tile's range at the last contributor of any pixel
-  int32_t wmax = my_last;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) wmax = max(wmax, __shfl_xor(wmax, m, 64));
-  if (lane == 0) s_maxlast[wid] = wmax;
-  __syncthreads();
-  const int32_t max_last = max(max(s_maxlast[0], s_maxlast[1]), max(s_maxlast[2], s_maxlast[3]));
+  const int32_t max_last = tile_max_last(my_last, s_maxlast, 4);
   const int64_t end = min(t.end, (int64_t)max_last + 1);
 
   // T_final (v_render_alpha - bg . v_out), this slab's share
@@ -315,7 +260,7 @@ __global__ void __launch_bounds__(256) wide_bwd_kernel(Args a, int nslab) {
   // |v_means2d| is not linear in q: it needs the pixel's whole v_alpha.  With
   // more than one slab, slab 0 also forms q over all channels (the operands of
   // the further slabs straight from global memory) and owns the abs fields.
-  const bool multi = ABS && nslab > 1 && t.slab == 0;
+  const bool multi = ABS && nslab > 1 && slab == 0;
   float fin_a = fin;
   int64_t pxs[4];
 #pragma unroll
@@ -396,43 +341,35 @@ __global__ void __launch_bounds__(256) wide_bwd_kernel(Args a, int nslab) {
     // 2. the scalar backward, lane = pixel; q[k][pixel] becomes w[k][pixel]
     for (int k = nb - 1; k >= 0; --k) {
       const int64_t idx = b0 + k;
-      const float2 xy = s.xy[k];
+      const float2 xy = s.xy[k];  // before cn: the order of the loads is that of the operands
       const float4 cn = s.con[k];
-      const float dx = xy.x - fx, dy = xy.y - fy;
-      const float sigma = 0.5f * cn.x * dx * dx + 0.5f * cn.z * dy * dy + cn.y * dx * dy;
-      const float ex = __expf(-sigma);
-      const float alpha_raw = cn.w * ex;
-      const bool valid = (idx <= my_last) && (sigma >= 0.f) && (alpha_raw >= kAlphaMin);
+      const BwdRecord r = bwd_record(xy, cn, px.fx, px.fy);
+      const bool valid = (idx <= my_last) && blends(r);
       float w = 0.f;
       if (__ballot(valid) != 0) {
         float g[NF];
 #pragma unroll
         for (int f = 0; f < NF; ++f) g[f] = 0.f;
         if (valid) {
-          const float alpha = fminf(kAlphaMax, alpha_raw);
+          const float alpha = fminf(kAlphaMax, r.alpha_raw);
           const float ra = 1.f / (1.f - alpha);
           T *= ra;
           w = alpha * T;
           const float q = s_qw[k * kWLd + tid];
           rD += q * w;
           float Dalpha = ra * (fin + T * q - rD);
-          if (alpha_raw > kAlphaMax) Dalpha = 0.f;  // a clamped alpha has no gradient
-          const float aD = alpha * Dalpha;
-          g[0] = Dalpha * ex;
-          g[1] = -aD * (cn.x * dx + cn.y * dy);
-          g[2] = -aD * (cn.y * dx + cn.z * dy);
-          g[3] = -0.5f * aD * dx * dx;
-          g[4] = -aD * dx * dy;
-          g[5] = -0.5f * aD * dy * dy;
+          if (r.alpha_raw > kAlphaMax) Dalpha = 0.f;  // a clamped alpha has no gradient
+          const GeomGrads gg = geom_grads(cn, r, alpha, Dalpha);
+          g[0] = gg.op, g[1] = gg.mx, g[2] = gg.my, g[3] = gg.ca, g[4] = gg.cb, g[5] = gg.cc;
           if constexpr (ABS) {
-            if (t.slab == 0) {
+            if (slab == 0) {
               const float qa = multi ? s_qa[k * kWLd + tid] : q;
               rD_a += qa * w;
               float Da = ra * (fin_a + T * qa - rD_a);
-              if (alpha_raw > kAlphaMax) Da = 0.f;
+              if (r.alpha_raw > kAlphaMax) Da = 0.f;
               const float aDa = alpha * Da;
-              g[6] = fabsf(aDa * (cn.x * dx + cn.y * dy));
-              g[7] = fabsf(aDa * (cn.y * dx + cn.z * dy));
+              g[6] = fabsf(aDa * (cn.x * r.dx + cn.y * r.dy));
+              g[7] = fabsf(aDa * (cn.y * r.dx + cn.z * r.dy));
             }
           }
         }
@@ -480,9 +417,8 @@ static int check(const char *who, int C, int D, int W, int H, int ts, int tw, in
                  int64_t n_isects) {
   GS_REQUIRE(ts == r16::kTS, "%s: tile_size %d is not supported (16 only)", who, ts);
   GS_REQUIRE(D >= kMinD && D <= kMaxD, "%s: %d channels not in [%d, %d]", who, D, kMinD, kMaxD);
-  GS_REQUIRE(C >= 0 && W >= 0 && H >= 0 && n_isects >= 0, "%s: negative sizes", who);
-  GS_REQUIRE((int64_t)tw * ts >= W && (int64_t)th * ts >= H,
-             "%s: tile grid %dx%d x %d does not cover %dx%d", who, tw, th, ts, W, H);
+  GS_REQUIRE(n_isects >= 0, "%s: negative sizes", who);
+  if (int e = check_tile_sizes(who, C, W, H, ts, tw, th)) return e;
   GS_REQUIRE((int64_t)C * tw * th * ((kMaxD + kBwdSlab - 1) / kBwdSlab) < (1ll << 31),
              "%s: too many tiles", who);
   return 0;
@@ -506,15 +442,10 @@ extern "C" int gsplat_hip_rasterize_wide_fwd(
   if (int e = wide::check("rasterize_wide_fwd", C, D, width, height, tile_size, tile_width,
                           tile_height, n_isects))
     return e;
-  wide::Args a{};
-  a.C = C; a.D = D; a.W = width; a.H = height; a.tw = tile_width; a.th = tile_height;
-  a.n_tiles = C * tile_width * tile_height;
+  const TileArgs a = tile_args(C, D, width, height, tile_size, tile_width, tile_height, means2d,
+                               conics, colors, opacities, backgrounds, masks, isect_offsets,
+                               n_isects, flatten_ids, render_colors, render_alphas, last_ids);
   if (a.n_tiles == 0) return 0;
-  a.n_isects = n_isects;
-  a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-  a.backgrounds = backgrounds; a.masks = masks; a.offsets = isect_offsets;
-  a.flatten_ids = flatten_ids;
-  a.render_colors = render_colors; a.render_alphas = render_alphas; a.last_ids = last_ids;
   const int nslab = (D + wide::kFwdSlab - 1) / wide::kFwdSlab;
   hipLaunchKernelGGL(wide::wide_fwd_kernel, dim3((unsigned)(a.n_tiles * nslab)), dim3(256), 0,
                      (hipStream_t)stream, a, nslab);
@@ -536,25 +467,13 @@ extern "C" int gsplat_hip_rasterize_wide_bwd(
     return e;
   GS_REQUIRE(n_gaussians >= 0, "rasterize_wide_bwd: negative sizes");
   hipStream_t st = (hipStream_t)stream;
-  const size_t G = (size_t)n_gaussians;
-  GS_HIP(gs::zero_async(v_means2d, sizeof(float) * 2 * G, st));
-  GS_HIP(gs::zero_async(v_conics, sizeof(float) * 3 * G, st));
-  GS_HIP(gs::zero_async(v_colors, sizeof(float) * D * G, st));
-  GS_HIP(gs::zero_async(v_opacities, sizeof(float) * G, st));
-  if (v_means2d_abs) GS_HIP(gs::zero_async(v_means2d_abs, sizeof(float) * 2 * G, st));
-  wide::Args a{};
-  a.C = C; a.D = D; a.W = width; a.H = height; a.tw = tile_width; a.th = tile_height;
-  a.n_tiles = C * tile_width * tile_height;
+  const TileArgs a = tile_args(C, D, width, height, tile_size, tile_width, tile_height, means2d,
+                               conics, colors, opacities, backgrounds, masks, isect_offsets,
+                               n_isects, flatten_ids, nullptr, const_cast<float *>(render_alphas),
+                               const_cast<int32_t *>(last_ids), v_render_colors, v_render_alphas,
+                               v_means2d, v_conics, v_colors, v_opacities, v_means2d_abs);
+  if (int e = zero_grads(a, n_gaussians, st)) return e;
   if (a.n_tiles == 0 || n_isects == 0) return 0;
-  a.n_isects = n_isects;
-  a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-  a.backgrounds = backgrounds; a.masks = masks; a.offsets = isect_offsets;
-  a.flatten_ids = flatten_ids;
-  a.render_alphas = const_cast<float *>(render_alphas);
-  a.last_ids = const_cast<int32_t *>(last_ids);
-  a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
-  a.v_means2d = v_means2d; a.v_conics = v_conics; a.v_colors = v_colors;
-  a.v_opacities = v_opacities; a.v_abs = v_means2d_abs;
   const int nslab = (D + wide::kBwdSlab - 1) / wide::kBwdSlab;
   const dim3 grid((unsigned)(a.n_tiles * nslab));
   if (v_means2d_abs)

@@ -26,8 +26,6 @@
 namespace gs {
 namespace surfel {
 
-constexpr float kAlphaMax = 0.999f;
-constexpr float kTMin = 1e-4f;
 constexpr float kFilterInvSquare = 2.f;  // FILTER_INV_SQUARE_2DGS, Rasterization.h:11
 constexpr float kLog2e = 1.4426950408889634f;
 

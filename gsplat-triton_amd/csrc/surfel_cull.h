@@ -2,12 +2,11 @@
 // a tile, csrc/surfel.hip) and the supertile isect emission's tile culling of
 // large surfels (csrc/isect_st.h, the captured 2DGS training step).
 #pragma once
-#include "common.h"
+#include "raster_tile.h"
 
 namespace gs {
 namespace surfel {
 
-constexpr float kAlphaMin = 1.f / 255.f;
 
 // Strip culling: false only if no pixel centre of [x0,x1]x[y0,y1] can reach
 // alpha >= 1/255, i.e. sigma = min(g3, g2) / 2 > ln(255 opacity) everywhere

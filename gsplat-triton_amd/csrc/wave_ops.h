@@ -1,11 +1,14 @@
 // Wave64 lane-exchange helpers shared by the rasterizers (gfx950).
 //
-// reduce_scatter<N>: the per-lane partial gradients of N <= 16 fields are
-// summed over the 64 lanes with permlane32/16 swaps, DPP row mirrors and quad
-// permutes; afterwards lane l holds the wave total of field rs_field(l) (the
-// four lanes of a quad hold the same total), so 16 lanes can issue one
-// coalesced atomic into a packed gradient row.
+// reduce_scatter<N, Op>: the per-lane partial gradients of N <= 16 fields are
+// summed (Op = Max: their maximum is taken) over the 64 lanes with
+// permlane32/16 swaps, DPP row mirrors and quad permutes; afterwards lane l
+// holds the wave total of field rs_field(l) (the four lanes of a quad hold
+// the same total), so 16 lanes can issue one coalesced atomic into a packed
+// gradient row.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -17,17 +20,6 @@ GS_INLINE float dpp(float v) {
       float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 
-
-GS_INLINE float swap32_sum(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-GS_INLINE float swap16_sum(float a, float b) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // Pair exchange of lane bit 3 / bit 2 with the reduction, selected by DPP
 // bank masks instead of per-lane selects (a bank is 4 lanes of a 16-lane
 // row).  add_b3(lo, hi): lanes with bit 3 clear (banks 0, 1) get
@@ -36,52 +28,81 @@ GS_INLINE float swap16_sum(float a, float b) {
 // 2 read lane + 4 = row_ror:12, banks 1, 3 lane - 4 = row_ror:4).  Two
 // v_add_f32_dpp per value; the select-based form took 2 v_cndmask_b32 more.
 // s_nop 1: the VALU-write -> DPP-read hazard needs two wait states, which the
-// compiler does not insert for inline asm.
-GS_INLINE float add_b3(float lo, float hi) {
-  float r;
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc"
-      : "=&v"(r)
-      : "v"(lo), "v"(hi));
-  return r;
-}
-GS_INLINE float add_b2(float lo, float hi) {
-  float r;
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
-      "v_add_f32_dpp %0, %2, %2 row_ror:4 row_mask:0xf bank_mask:0xa"
-      : "=&v"(r)
-      : "v"(lo), "v"(hi));
-  return r;
-}
+// compiler does not insert for inline asm.  max_b3 / max_b2: v_max_f32_dpp.
+#define GS_DPP_PAIR_STEP(name, op, ror_lo, bank_lo, ror_hi, bank_hi)                   \
+  GS_INLINE float name(float lo, float hi) {                                           \
+    float r;                                                                           \
+    asm("s_nop 1\n\t"                                                                  \
+        op " %0, %1, %1 row_ror:" #ror_lo " row_mask:0xf bank_mask:" #bank_lo "\n\t"   \
+        op " %0, %2, %2 row_ror:" #ror_hi " row_mask:0xf bank_mask:" #bank_hi          \
+        : "=&v"(r)                                                                     \
+        : "v"(lo), "v"(hi));                                                           \
+    return r;                                                                          \
+  }
+#define GS_DPP_PAIR_STEPS(prefix, op)               \
+  GS_DPP_PAIR_STEP(prefix##_b3, op, 8, 0x3, 8, 0xc) \
+  GS_DPP_PAIR_STEP(prefix##_b2, op, 12, 0x5, 4, 0xa)
+GS_DPP_PAIR_STEPS(add, "v_add_f32_dpp")
+GS_DPP_PAIR_STEPS(max, "v_max_f32_dpp")
+#undef GS_DPP_PAIR_STEPS
+#undef GS_DPP_PAIR_STEP
 
-// Reduce-scatter of N <= 16 per-lane values over the wave: every lane ends
-// with the wave-wide total of field rs_field(lane).  Fields are paired
-// adjacently at each halving (lane bits 5, 4, 3, 2 choose the half), so an
-// odd count costs no padded swaps: 9 fields take 5 + 3 + 2 + 1 combining
-// steps plus two quad adds.
+// The combining operation of a reduce_scatter: of two values, and its
+// bank-masked DPP steps for lane bits 3 and 2.
+struct Sum {
+  static GS_INLINE float combine(float a, float b) { return a + b; }
+  static GS_INLINE float b3(float lo, float hi) { return add_b3(lo, hi); }
+  static GS_INLINE float b2(float lo, float hi) { return add_b2(lo, hi); }
+};
+struct Max {
+  static GS_INLINE float combine(float a, float b) { return fmaxf(a, b); }
+  static GS_INLINE float b3(float lo, float hi) { return max_b3(lo, hi); }
+  static GS_INLINE float b2(float lo, float hi) { return max_b2(lo, hi); }
+};
+
+// Lanes l and l ^ 32 (swap16: l ^ 16) exchange one value each, the lower lane
+// its b and the upper its a, and combine the pair they now hold.
+template <class Op = Sum>
+GS_INLINE float swap32(float a, float b) {
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return Op::combine(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+template <class Op = Sum>
+GS_INLINE float swap16(float a, float b) {
+  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return Op::combine(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+GS_INLINE float swap32_sum(float a, float b) { return swap32(a, b); }
+GS_INLINE float swap16_sum(float a, float b) { return swap16(a, b); }
+
 // a[i] for i < M, else 0 (index clamped so that no access is out of range)
 template <int M>
 GS_INLINE float pick(const float (&a)[M], int i) {
   return i < M ? a[i < M ? i : 0] : 0.f;
 }
 
-template <int N>
+// Reduce-scatter of N <= 16 per-lane values over the wave: every lane ends
+// with the wave-wide total (Op: sum, or Max) of field rs_field(lane), the
+// same field whatever the Op.  Fields are paired adjacently at each halving
+// (lane bits 5, 4, 3, 2 choose the half), so an odd count costs no padded
+// swaps: 9 fields take 5 + 3 + 2 + 1 combining steps plus two quad steps.
+template <int N, class Op = Sum>
 GS_INLINE float reduce_scatter(const float *v, int lane) {
   static_assert(N >= 1 && N <= 16, "reduce_scatter: 1..16 fields");
+  static_assert(N == 16 || std::is_same<Op, Sum>::value,
+                "reduce_scatter: a missing field is padded with 0, the identity of Sum only");
   constexpr int N1 = (N + 1) / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2;
   float w[N1], x[N2], y[N3];
 #pragma unroll
-  for (int i = 0; i < N1; ++i) w[i] = swap32_sum(v[2 * i], 2 * i + 1 < N ? v[2 * i + 1] : 0.f);
+  for (int i = 0; i < N1; ++i) w[i] = swap32<Op>(v[2 * i], 2 * i + 1 < N ? v[2 * i + 1] : 0.f);
 #pragma unroll
-  for (int i = 0; i < N2; ++i) x[i] = swap16_sum(w[2 * i], pick(w, 2 * i + 1));
+  for (int i = 0; i < N2; ++i) x[i] = swap16<Op>(w[2 * i], pick(w, 2 * i + 1));
   (void)lane;
 #pragma unroll
-  for (int i = 0; i < N3; ++i) y[i] = add_b3(x[2 * i], pick(x, 2 * i + 1));  // bit 3
-  float z = add_b2(y[0], pick(y, 1));  // bit 2
-  z += dpp<0xB1>(z);  // quad lane ^ 1
-  z += dpp<0x4E>(z);  // quad lane ^ 2
+  for (int i = 0; i < N3; ++i) y[i] = Op::b3(x[2 * i], pick(x, 2 * i + 1));  // bit 3
+  float z = Op::b2(y[0], pick(y, 1));  // bit 2
+  z = Op::combine(z, dpp<0xB1>(z));  // quad lane ^ 1
+  z = Op::combine(z, dpp<0x4E>(z));  // quad lane ^ 2
   return z;
 }
 

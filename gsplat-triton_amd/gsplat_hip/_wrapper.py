@@ -978,6 +978,48 @@ def sh_colors(sh_degree: int, means: Tensor, viewmats: Tensor, coeffs, radii: Te
 
 
 # ============================================================ rasterization ==
+# The prologues and epilogues that _RasterizeToPixels and _RasterizeToPixelsWide
+# share; they leave width, height, tile_size, absgrad and means2d_in on `ctx`.
+def _raster_fwd_begin(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
+                      tile_size, isect_offsets, flatten_ids, absgrad):
+    ctx.means2d_in = means2d if absgrad else None  # receives .absgrad (_wrapper.py:156)
+    ctx.set_materialize_grads(False)  # alphas without a loss: None, not zeros
+    ctx.width, ctx.height, ctx.tile_size, ctx.absgrad = width, height, tile_size, absgrad
+    means2d, conics, colors, opacities, backgrounds = (
+        _f32c(x) for x in (means2d, conics, colors, opacities, backgrounds))
+    _dev_check(means2d, conics, colors, opacities, isect_offsets, flatten_ids)
+    isect_offsets = isect_offsets.to(torch.int32).contiguous()
+    flatten_ids = flatten_ids.to(torch.int32).contiguous()
+    m = None if masks is None else masks.to(torch.bool).contiguous()
+    C, D, dev = isect_offsets.shape[0], colors.shape[-1], means2d.device
+    render_colors = torch.empty((C, height, width, D), device=dev)
+    render_alphas = torch.empty((C, height, width, 1), device=dev)
+    last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev)
+    return (means2d, conics, colors, opacities, backgrounds, m, isect_offsets, flatten_ids,
+            render_colors, render_alphas, last_ids)
+
+
+def _raster_bwd_begin(ctx, v_render_colors, v_render_alphas, render_alphas, means2d, conics,
+                      colors, opacities):
+    """The cotangents as the ABI takes them (v_render_alphas None: alphas unused, null there)
+    and the gradient buffers in its order: means2d, conics, colors, opacities, means2d_abs."""
+    if v_render_colors is None:
+        v_render_colors = render_alphas.new_zeros(*render_alphas.shape[:3], colors.shape[-1])
+    grads = (torch.empty_like(means2d), torch.empty_like(conics), torch.empty_like(colors),
+             torch.empty_like(opacities), torch.empty_like(means2d) if ctx.absgrad else None)
+    return _f32c(v_render_colors), _f32c(v_render_alphas), grads
+
+
+def _raster_bwd_end(ctx, grads, v_render_colors, render_alphas):
+    """The gradients of backward()'s first five inputs; v_means2d_abs goes to means2d.absgrad."""
+    if ctx.absgrad:
+        ctx.means2d_in.absgrad = grads[4]
+    v_backgrounds = None
+    if ctx.needs_input_grad[4]:
+        v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
+    return grads[:4] + (v_backgrounds,)
+
+
 class _RasterizeToPixels(torch.autograd.Function):
     """Rasterize Gaussians (gsplat/triton_impl/_wrapper.py:42-182)."""
 
@@ -985,25 +1027,17 @@ class _RasterizeToPixels(torch.autograd.Function):
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
                 tile_size, isect_offsets, flatten_ids, absgrad, block_size=8, visible=None,
                 records=None, n_dev=None, ranks=None):
-        ctx.means2d_in = means2d if absgrad else None  # receives .absgrad (_wrapper.py:156)
-        ctx.set_materialize_grads(False)  # alphas without a loss: None, not zeros
-        means2d, conics, colors, opacities, backgrounds = (
-            _f32c(x) for x in (means2d, conics, colors, opacities, backgrounds))
-        _dev_check(means2d, conics, colors, opacities, isect_offsets, flatten_ids)
-        isect_offsets = isect_offsets.to(torch.int32).contiguous()
-        flatten_ids = flatten_ids.to(torch.int32).contiguous()
-        m = None if masks is None else masks.to(torch.bool).contiguous()
+        (means2d, conics, colors, opacities, backgrounds, m, isect_offsets, flatten_ids,
+         render_colors, render_alphas, last_ids) = _raster_fwd_begin(
+            ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
+            tile_size, isect_offsets, flatten_ids, absgrad)
         C, th, tw = isect_offsets.shape
         D = colors.shape[-1]
-        dev = means2d.device
-        render_colors = torch.empty((C, height, width, D), device=dev)
-        render_alphas = torch.empty((C, height, width, 1), device=dev)
-        last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev)
         # compositing state at the chunk boundaries of long tiles, for the
         # chunked backward (csrc/rasterize16.hip); empty when not used
         sb = int(_lib.query("gsplat_hip_rasterize_fwd_state_bytes", C, D, tile_size, tw, th,
                             flatten_ids.numel()))
-        state = torch.empty(sb // 4, dtype=torch.float32, device=dev)
+        state = torch.empty(sb // 4, dtype=torch.float32, device=means2d.device)
         # one 64-B render record per Gaussian for the 16x16 kernels' gathers
         # (rasterization() may have packed them already, before its isect sync)
         if records is None:
@@ -1029,7 +1063,6 @@ class _RasterizeToPixels(torch.autograd.Function):
         ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, m, isect_offsets,
                               kernel_ids, render_alphas, last_ids, render_colors, state, records,
                               vis_rank)
-        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad = width, height, tile_size, absgrad
         ctx.n_dev = n_dev
         # tiles_per_gauss: the backward zeroes / reads only those rows
         ctx.visible = None if visible is None else visible.to(torch.int32).contiguous()
@@ -1044,15 +1077,9 @@ class _RasterizeToPixels(torch.autograd.Function):
         C, th, tw = isect_offsets.shape
         D = colors.shape[-1]
         G = opacities.numel()
-        if v_render_colors is None:
-            v_render_colors = torch.zeros_like(render_colors)
-        v_render_colors = _f32c(v_render_colors)
-        v_render_alphas = _f32c(v_render_alphas)  # None: alphas unused (null in the ABI)
-        v_means2d = torch.empty_like(means2d)
-        v_conics = torch.empty_like(conics)
-        v_colors = torch.empty_like(colors)
-        v_opacities = torch.empty_like(opacities)
-        v_abs = torch.empty_like(means2d) if ctx.absgrad else None
+        v_render_colors, v_render_alphas, grads = _raster_bwd_begin(
+            ctx, v_render_colors, v_render_alphas, render_alphas, means2d, conics, colors,
+            opacities)
         wsb = int(_lib.query("gsplat_hip_rasterize_bwd_workspace_bytes", G, D, ctx.tile_size,
                              int(bool(ctx.absgrad)), C, tw, th, flatten_ids.numel()))
         ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=means2d.device)
@@ -1061,19 +1088,12 @@ class _RasterizeToPixels(torch.autograd.Function):
                       tw, th, _ptr(means2d), _ptr(conics), _ptr(colors), _ptr(opacities),
                       _ptr(backgrounds), _ptr(m), _ptr(isect_offsets), flatten_ids.numel(),
                       _ptr(ctx.n_dev), _ptr(flatten_ids), _ptr(render_alphas), _ptr(last_ids),
-                      _ptr(v_render_colors), _ptr(v_render_alphas), _ptr(v_means2d),
-                      _ptr(v_conics), _ptr(v_colors), _ptr(v_opacities), _ptr(v_abs),
+                      _ptr(v_render_colors), _ptr(v_render_alphas), *map(_ptr, grads),
                       _ptr(render_colors), _ptr(records) if records.numel() else 0,
                       _ptr(state) if state.numel() else 0, state.numel() * 4, _ptr(ws), wsb,
                       _ptr(ctx.visible), _ptr(vis_rank if ctx.visible is not None else None),
                       _stream())
-        if ctx.absgrad:
-            ctx.means2d_in.absgrad = v_abs
-        v_backgrounds = None
-        if ctx.needs_input_grad[4]:
-            v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
-        return (v_means2d, v_conics, v_colors, v_opacities, v_backgrounds,
-                None, None, None, None, None, None, None, None, None, None, None, None)
+        return _raster_bwd_end(ctx, grads, v_render_colors, render_alphas) + (None,) * 12
 
 
 class _RasterizeToPixelsWide(torch.autograd.Function):
@@ -1084,20 +1104,12 @@ class _RasterizeToPixelsWide(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
                 tile_size, isect_offsets, flatten_ids, absgrad):
-        ctx.means2d_in = means2d if absgrad else None  # receives .absgrad
-        ctx.set_materialize_grads(False)  # alphas without a loss: None, not zeros
-        means2d, conics, colors, opacities, backgrounds = (
-            _f32c(x) for x in (means2d, conics, colors, opacities, backgrounds))
-        _dev_check(means2d, conics, colors, opacities, isect_offsets, flatten_ids)
-        isect_offsets = isect_offsets.to(torch.int32).contiguous()
-        flatten_ids = flatten_ids.to(torch.int32).contiguous()
-        m = None if masks is None else masks.to(torch.bool).contiguous()
+        (means2d, conics, colors, opacities, backgrounds, m, isect_offsets, flatten_ids,
+         render_colors, render_alphas, last_ids) = _raster_fwd_begin(
+            ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height,
+            tile_size, isect_offsets, flatten_ids, absgrad)
         C, th, tw = isect_offsets.shape
         D = colors.shape[-1]
-        dev = means2d.device
-        render_colors = torch.empty((C, height, width, D), device=dev)
-        render_alphas = torch.empty((C, height, width, 1), device=dev)
-        last_ids = torch.empty((C, height, width), dtype=torch.int32, device=dev)
         with _Timed("rasterize_wide_fwd"):
             _lib.call("gsplat_hip_rasterize_wide_fwd", C, D, width, height, tile_size, tw, th,
                       _ptr(means2d), _ptr(conics), _ptr(colors), _ptr(opacities),
@@ -1106,7 +1118,6 @@ class _RasterizeToPixelsWide(torch.autograd.Function):
                       _ptr(last_ids), _stream())
         ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, m, isect_offsets,
                               flatten_ids, render_alphas, last_ids)
-        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad = width, height, tile_size, absgrad
         return render_colors, render_alphas
 
     @staticmethod
@@ -1115,30 +1126,17 @@ class _RasterizeToPixelsWide(torch.autograd.Function):
          render_alphas, last_ids) = ctx.saved_tensors
         C, th, tw = isect_offsets.shape
         D = colors.shape[-1]
-        if v_render_colors is None:
-            v_render_colors = torch.zeros((C, ctx.height, ctx.width, D), device=means2d.device)
-        v_render_colors = _f32c(v_render_colors)
-        v_render_alphas = _f32c(v_render_alphas)  # None: alphas unused (null in the ABI)
-        v_means2d = torch.empty_like(means2d)
-        v_conics = torch.empty_like(conics)
-        v_colors = torch.empty_like(colors)
-        v_opacities = torch.empty_like(opacities)
-        v_abs = torch.empty_like(means2d) if ctx.absgrad else None
+        v_render_colors, v_render_alphas, grads = _raster_bwd_begin(
+            ctx, v_render_colors, v_render_alphas, render_alphas, means2d, conics, colors,
+            opacities)
         with _Timed("rasterize_wide_bwd"):
             _lib.call("gsplat_hip_rasterize_wide_bwd", C, opacities.numel(), D, ctx.width,
                       ctx.height, ctx.tile_size, tw, th, _ptr(means2d), _ptr(conics),
                       _ptr(colors), _ptr(opacities), _ptr(backgrounds), _ptr(m),
                       _ptr(isect_offsets), flatten_ids.numel(), _ptr(flatten_ids),
                       _ptr(render_alphas), _ptr(last_ids), _ptr(v_render_colors),
-                      _ptr(v_render_alphas), _ptr(v_means2d), _ptr(v_conics), _ptr(v_colors),
-                      _ptr(v_opacities), _ptr(v_abs), _stream())
-        if ctx.absgrad:
-            ctx.means2d_in.absgrad = v_abs
-        v_backgrounds = None
-        if ctx.needs_input_grad[4]:
-            v_backgrounds = (v_render_colors * (1.0 - render_alphas)).sum(dim=(1, 2))
-        return (v_means2d, v_conics, v_colors, v_opacities, v_backgrounds,
-                None, None, None, None, None, None, None)
+                      _ptr(v_render_alphas), *map(_ptr, grads), _stream())
+        return _raster_bwd_end(ctx, grads, v_render_colors, render_alphas) + (None,) * 7
 
 
 def rasterize_to_pixels(

@@ -277,3 +277,29 @@ def test_edge_values_vs_float64_oracle(ts, D):
     dead = case.opacities.reshape(-1) < 1 / 255
     for k in ("v_means2d", "v_conics", "v_colors", "v_opacities", "v_means2d_abs"):
         assert not got[k].reshape(case.N, -1)[dead].any(), k
+
+
+def test_nan_sigma_is_skipped_forward_and_backward():
+    """A record whose sigma is NaN (a non-finite conic) is not blended by the
+    workgroup-per-tile kernels (`sigma >= 0 && alpha >= 1/255`, csrc/raster_tile.h),
+    forward and backward alike: the render is the one with that Gaussian's
+    opacity at 0, bit for bit, and its gradient rows are exactly zero (all
+    outputs finite: asserted in _render)."""
+    import types
+    base = _case("edge", 8, 2)
+    ids = base.flatten_ids
+    solid = np.flatnonzero(base.opacities.reshape(-1) >= 0.5)
+    g = int(solid[np.argmax(np.bincount(ids, minlength=base.N)[solid])])
+    assert (ids == g).sum() > 1
+    nan = types.SimpleNamespace(**vars(base))
+    nan.conics = base.conics.copy()
+    nan.conics.reshape(-1, 3)[g] = np.nan
+    off = types.SimpleNamespace(**vars(base))
+    off.opacities = base.opacities.copy()
+    off.opacities.reshape(-1)[g] = 0.0
+    got, ref = _render(nan), _render(off)
+    for k in ("colors", "alphas", "last_ids"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert not np.array_equal(got["colors"], _render(base, backward=False)["colors"])
+    for k in ("v_means2d", "v_conics", "v_colors", "v_opacities", "v_means2d_abs"):
+        assert not got[k].reshape(base.N, -1)[g].any(), k
