@@ -27,6 +27,7 @@
 
 #include "isect_st.h"
 #include "lsd_sort.h"
+#include "scan_ops.h"
 #include "wave_ops.h"
 
 namespace gs {
@@ -57,47 +58,21 @@ GS_INLINE int tiles_of(const float *means2d, const int32_t *radii, int64_t i, in
   return (rect->x1 - rect->x0) * (rect->y1 - rect->y0);
 }
 
-template <typename T>
-GS_INLINE T block_exclusive_scan(T v, T *lds /* [kIsectBlock/64 + 1] */, T *total) {
-  // wave-level inclusive scan with shuffles, then across the 4 waves via LDS
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    T y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[wid] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T run = 0;
-    for (int w = 0; w < kIsectBlock / 64; ++w) {
-      T s = lds[w];
-      lds[w] = run;
-      run += s;
-    }
-    lds[kIsectBlock / 64] = run;
-  }
-  __syncthreads();
-  *total = lds[kIsectBlock / 64];
-  return lds[wid] + x - v;
-}
-
 // Per-Gaussian tile counts; per-block sums of the counts (block_sums[b]) and
 // of the number of Gaussians with at least one tile (vis_sums[b]).
 __global__ void __launch_bounds__(kIsectBlock)
 isect_count_kernel(int64_t G, const float *__restrict__ means2d, const int32_t *__restrict__ radii,
                    int ts, int tw, int th, int32_t *__restrict__ tiles_per_gauss,
                    int64_t *__restrict__ block_sums, int64_t *__restrict__ vis_sums) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   const int64_t i = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x;
   Rect rc;
   int cnt = (i < G) ? tiles_of(means2d, radii, i, ts, tw, th, &rc) : 0;
   if (i < G) tiles_per_gauss[i] = cnt;
   int64_t tot, vtot;
-  block_exclusive_scan<int64_t>((int64_t)cnt, lds, &tot);
+  block_exclusive_scan((int64_t)cnt, lds, tot);
   __syncthreads();
-  block_exclusive_scan<int64_t>((int64_t)(cnt > 0), lds, &vtot);
+  block_exclusive_scan((int64_t)(cnt > 0), lds, vtot);
   if (threadIdx.x == 0) {
     block_sums[blockIdx.x] = tot;
     vis_sums[blockIdx.x] = vtot;
@@ -116,41 +91,10 @@ __global__ void __launch_bounds__(1024) isect_scan_blocks_kernel(int64_t nb, int
                                                                  int64_t *totals) {
   int64_t *block_sums = blockIdx.x == 0 ? first : second;
   __shared__ int64_t wave_tot[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int64_t carry = 0;  // identical in every lane
-  for (int64_t base = 0; base < nb; base += 1024 * kScanK) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * kScanK;
-    int64_t v[kScanK], s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanK; ++k) v[k] = (i0 + k < nb) ? block_sums[i0 + k] : 0;
-#pragma unroll
-    for (int k = 0; k < kScanK; ++k) s += v[k];
-    int64_t x = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wave_tot[wid] = x;
-    __syncthreads();
-    int64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      before += w < wid ? wave_tot[w] : 0;
-      all += wave_tot[w];
-    }
-    int64_t run = carry + before + x - s;
-#pragma unroll
-    for (int k = 0; k < kScanK; ++k) {
-      if (i0 + k < nb) block_sums[i0 + k] = run;
-      run += v[k];
-    }
-    carry += all;
-    __syncthreads();
-  }
+  const int64_t total = array_exclusive_scan<int64_t, kScanK>(block_sums, nb, wave_tot);
   if (threadIdx.x == 0) {
-    block_sums[nb] = carry;
-    if (totals) totals[blockIdx.x] = carry;
+    block_sums[nb] = total;
+    if (totals) totals[blockIdx.x] = total;
   }
 }
 
@@ -160,12 +104,12 @@ isect_write_kernel(int64_t G, int N, const float *__restrict__ means2d,
                    const int32_t *__restrict__ camera_ids, int ts, int tw, int th, int tile_bits,
                    const int64_t *__restrict__ block_prefix, int64_t *__restrict__ isect_ids,
                    int32_t *__restrict__ flatten_ids) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   const int64_t i = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x;
   Rect rc{0, 0, 0, 0};
   const int cnt = (i < G) ? tiles_of(means2d, radii, i, ts, tw, th, &rc) : 0;
   int64_t tot;
-  const int64_t local = block_exclusive_scan<int64_t>((int64_t)cnt, lds, &tot);
+  const int64_t local = block_exclusive_scan((int64_t)cnt, lds, tot);
   if (cnt == 0) return;
   int64_t cur = block_prefix[blockIdx.x] + local;
   const int64_t cam = camera_ids ? (int64_t)camera_ids[i] : (i / N);
@@ -267,12 +211,12 @@ __global__ void __launch_bounds__(kIsectBlock)
 isect_compact_kernel(int64_t G, const int32_t *__restrict__ tiles_per_gauss,
                      const float *__restrict__ depths, const int64_t *__restrict__ vis_prefix,
                      int32_t *__restrict__ V, uint32_t *__restrict__ dkey, CapCheck cc) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   if (cc.cap_state && blockIdx.x == 0 && threadIdx.x == 0) cap_check(cc);
   const int64_t i = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x;
   const int on = (i < G) && tiles_per_gauss[i] > 0;
   int64_t tot;
-  const int64_t local = block_exclusive_scan<int64_t>((int64_t)on, lds, &tot);
+  const int64_t local = block_exclusive_scan((int64_t)on, lds, tot);
   if (!on) return;
   const int64_t s = vis_prefix[blockIdx.x] + local;
   V[s] = (int32_t)i;
@@ -285,13 +229,13 @@ isect_sorted_count_kernel(int64_t nV, const int64_t *__restrict__ nV_dev,
                           const int32_t *__restrict__ Vs,
                           const int32_t *__restrict__ tiles_per_gauss,
                           int64_t *__restrict__ block_sums, int32_t *__restrict__ n_big) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   if (nV_dev) nV = min(nV, *nV_dev);
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_big = 0;  // big list of the emit kernel
   const int64_t s = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x;
   const int cnt = (s < nV) ? tiles_per_gauss[Vs[s]] : 0;
   int64_t tot;
-  block_exclusive_scan<int64_t>((int64_t)cnt, lds, &tot);
+  block_exclusive_scan((int64_t)cnt, lds, tot);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -319,7 +263,7 @@ isect_sorted_emit_kernel(int64_t nV, int N, const int32_t *__restrict__ Vs,
                          const int64_t *__restrict__ block_prefix, uint32_t *__restrict__ tkey,
                          int32_t *__restrict__ val, BigEmit *__restrict__ big_list,
                          int32_t *__restrict__ n_big, const int64_t *__restrict__ cap_state) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   // capacity mode: cap_state = {n_isects if it fits else 0, n_visible,
   // overflow of this call}; nothing is written past the arrays on overflow
   if (cap_state) {
@@ -336,7 +280,7 @@ isect_sorted_emit_kernel(int64_t nV, int N, const int32_t *__restrict__ Vs,
     cnt = tiles_of(means2d, radii, i, ts, tw, th, &rc);
   }
   int64_t tot;
-  const int64_t local = block_exclusive_scan<int64_t>((int64_t)cnt, lds, &tot);
+  const int64_t local = block_exclusive_scan((int64_t)cnt, lds, tot);
   const int64_t cur0 = block_prefix[blockIdx.x] + local;
   uint32_t hi = key_all_ones;  // all ones: negative depth (every tile gets the all-ones key)
   if (cnt > 0 && __float_as_int(depths[i]) >= 0)
@@ -869,12 +813,12 @@ isect_write_tiles_kernel(int64_t G, int N, const float *__restrict__ means2d,
                          int tile_bits, uint32_t key_all_ones,
                          const int64_t *__restrict__ block_prefix, uint32_t *__restrict__ tkey,
                          int32_t *__restrict__ val) {
-  __shared__ int64_t lds[kIsectBlock / 64 + 1];
+  __shared__ int64_t lds[kIsectBlock / 64];
   const int64_t i = (int64_t)blockIdx.x * kIsectBlock + threadIdx.x;
   Rect rc{0, 0, 0, 0};
   const int cnt = (i < G) ? tiles_of(means2d, radii, i, ts, tw, th, &rc) : 0;
   int64_t tot;
-  const int64_t local = block_exclusive_scan<int64_t>((int64_t)cnt, lds, &tot);
+  const int64_t local = block_exclusive_scan((int64_t)cnt, lds, tot);
   if (cnt == 0) return;
   int64_t cur = block_prefix[blockIdx.x] + local;
   const uint32_t cam = camera_ids ? (uint32_t)camera_ids[i] : (uint32_t)(i / N);

@@ -44,6 +44,7 @@
 #pragma once
 #include "common.h"
 #include "lsd_sort.h"
+#include "scan_ops.h"
 #include "surfel_cull.h"
 
 namespace gs {
@@ -96,28 +97,6 @@ GS_INLINE uint32_t st_mask(const ushort4 r, int tx0, int ty0) {
   return m;
 }
 
-template <typename T>
-GS_INLINE T block_excl_scan256(T v, T *lds /* [5] */, T *total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[wid] = x;
-  __syncthreads();
-  T before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    before += w < wid ? lds[w] : (T)0;
-    all += lds[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
-
 // capacity state of the sync-free isect (isect.hip cap_check): {n written or
 // 0, n_visible, overflow, n}; null in the synchronous path
 GS_INLINE bool void_call(const int64_t *cap) { return cap && cap[2]; }
@@ -129,7 +108,7 @@ rect_kernel(int64_t nV, const int64_t *__restrict__ cap, const int32_t *__restri
             const int32_t *__restrict__ radii, int ts, Geo geo, ushort4 *__restrict__ rect,
             int64_t *__restrict__ blk, int32_t *__restrict__ vis_rank,
             int32_t *__restrict__ n_huge) {
-  __shared__ int64_t lds[5];
+  __shared__ int64_t lds[4];
   // the ranks are written even when the call is void (an overflow): the
   // rasterizer's record packing and gradient rows read them for every
   // Gaussian with a tile
@@ -153,7 +132,7 @@ rect_kernel(int64_t nV, const int64_t *__restrict__ cap, const int32_t *__restri
     else np = ((x1 - 1) / S - x0 / S + 1) * ((y1 - 1) / S - y0 / S + 1);
   }
   int64_t tot;
-  block_excl_scan256<int64_t>((int64_t)np, lds, &tot);
+  block_exclusive_scan((int64_t)np, lds, tot);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -177,7 +156,7 @@ emit_kernel(int64_t nV, const int64_t *__restrict__ cap, const int32_t *__restri
             const int32_t *__restrict__ camera_ids, Geo geo, const int64_t *__restrict__ blk_prefix,
             uint32_t *__restrict__ pkey, int32_t *__restrict__ pval,
             HugeEmit *__restrict__ huge_list, int32_t *__restrict__ n_huge) {
-  __shared__ int64_t lds[5];
+  __shared__ int64_t lds[4];
   if (cap) nV = void_call(cap) ? 0 : min(nV, cap[1]);
   const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -195,7 +174,7 @@ emit_kernel(int64_t nV, const int64_t *__restrict__ cap, const int32_t *__restri
                 : (uint32_t)(cam_of(camera_ids, geo.N, Vs[s]) * geo.nst1);
   }
   int64_t tot;
-  const int64_t cur0 = blk_prefix[blockIdx.x] + block_excl_scan256<int64_t>((int64_t)np, lds, &tot);
+  const int64_t cur0 = blk_prefix[blockIdx.x] + block_exclusive_scan((int64_t)np, lds, tot);
   if (np > 0 && np <= kLanePairs) {
     for (int k = 0; k < np; ++k) {
       const int yy = k / w, xx = k - yy * w;
@@ -361,16 +340,9 @@ plan_kernel(int nst, const uint32_t *__restrict__ totals, int32_t *__restrict__ 
     c[j] = d < nst ? (int)totals[d] : 0;
     sg[j] = (c[j] + kSeg - 1) / kSeg;
   }
-  int a = c[0] + c[1], b = sg[0] + sg[1];
-  int xa = a, xb = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ya = __shfl_up(xa, o, 64), yb = __shfl_up(xb, o, 64);
-    if (lane >= o) {
-      xa += ya;
-      xb += yb;
-    }
-  }
+  // the two scans share one barrier (two block_exclusive_scan calls: two)
+  const int a = c[0] + c[1], b = sg[0] + sg[1];
+  const int xa = wave_inclusive_scan(a), xb = wave_inclusive_scan(b);
   if (lane == 63) {
     wa[wid] = xa;
     wb[wid] = xb;
@@ -528,7 +500,7 @@ tile_scan_kernel(Geo geo, const int64_t *__restrict__ cap, int32_t *__restrict__
   __shared__ int32_t wsum[16];
   const int T = geo.C * geo.n_tiles;
   const int nt = T + 1;
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int t = threadIdx.x;
   const bool vd = void_call(cap);
   int carry = 0;
   for (int base = 0; base < nt; base += R) {
@@ -544,20 +516,8 @@ tile_scan_kernel(Geo geo, const int64_t *__restrict__ cap, int32_t *__restrict__
       v[k] = buf[t * PT + k];
       sum += v[k];
     }
-    int x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    int run = carry + x - sum, all = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      run += w < wid ? wsum[w] : 0;
-      all += wsum[w];
-    }
+    int all;
+    int run = carry + block_exclusive_scan(sum, wsum, all);
 #pragma unroll
     for (int k = 0; k < PT; ++k) {
       buf[t * PT + k] = run;
@@ -573,8 +533,8 @@ tile_scan_kernel(Geo geo, const int64_t *__restrict__ cap, int32_t *__restrict__
         if (i < T) offsets[i] = vd ? 0 : o;
       }
     }
-    carry = all;
-    __syncthreads();
+    carry += all;
+    __syncthreads();  // buf and wsum are written again in the next round
   }
   // tile culling (SurfelCull): the isects written -- fewer than the count of
   // the tile rectangles -- are the count the rasterizer reads on the device
@@ -636,12 +596,7 @@ seg_write_kernel(Geo geo, const int64_t *__restrict__ cap, const int32_t *__rest
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int c = (int)wp.m[e];
-      int x = c;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-      }
+      const int x = wave_inclusive_scan(c);
       const int pos = cur[0] + x - c;
       const int64_t id = (int64_t)(int32_t)db[e];
       for (int k = 0; k < c; ++k) {

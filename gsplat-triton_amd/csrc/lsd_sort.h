@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "scan_ops.h"
 
 namespace gs {
 namespace lsd {
@@ -95,36 +96,14 @@ hist_kernel(const uint32_t *__restrict__ keys, int64_t n, const int64_t *__restr
 // Device count: only the tiles holding items (tile = tile_items items).
 // (static: the one kernel here that is no template, and more than one source
 // file includes this header)
-static __global__ void __launch_bounds__(NT)
+static __global__ void __launch_bounds__(1024)
 scan_kernel(uint32_t *__restrict__ hist, int64_t nt, uint32_t *__restrict__ totals,
             const int64_t *__restrict__ n_dev, int64_t n, int64_t tile_items) {
-  __shared__ uint32_t wsum[NT / 64];
+  __shared__ uint32_t wave_tot[16];
   uint32_t *row = hist + (int64_t)blockIdx.x * nt;
   if (n_dev) nt = min(nt, (min(n, *n_dev) + tile_items - 1) / tile_items);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (int64_t b0 = 0; b0 < nt; b0 += NT) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nt ? row[i] : 0u;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    uint32_t before = carry, all = carry;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-      before += w < wid ? wsum[w] : 0u;
-      all += wsum[w];
-    }
-    if (i < nt) row[i] = before + x - v;
-    carry = all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+  const uint32_t sum = array_exclusive_scan<uint32_t, 1>(row, nt, wave_tot);
+  if (threadIdx.x == 0) totals[blockIdx.x] = sum;
 }
 
 // Stable in-tile ranking without sorting the tile: wave w owns the items
@@ -202,28 +181,11 @@ scatter_kernel(const uint32_t *__restrict__ kin, const int32_t *__restrict__ vin
     gv[j] = totals[d];
     gsum += gv[j];
   }
-  uint32_t x = tsum, g = gsum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64), z = __shfl_up(g, o, 64);
-    if (lane >= o) {
-      x += y;
-      g += z;
-    }
-  }
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  uint32_t lbefore = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) lbefore += w < wid ? wsum[w] : 0u;
-  uint32_t lrun = lbefore + x - tsum;  // tile slot of digit t*DPT's first item
-  __syncthreads();
-  if (lane == 63) wsum[wid] = g;
-  __syncthreads();
-  uint32_t gbefore = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) gbefore += w < wid ? wsum[w] : 0u;
-  uint32_t grun = gbefore + g - gsum;  // global start of digit t*DPT
+  // tile slot of digit t*DPT's first item, then the global start of digit t*DPT
+  uint32_t all;
+  uint32_t lrun = block_exclusive_scan(tsum, wsum, all);
+  __syncthreads();  // wsum is written again
+  uint32_t grun = block_exclusive_scan(gsum, wsum, all);
 #pragma unroll
   for (int j = 0; j < DPT; ++j) {
     const int d = t * DPT + j;
@@ -300,7 +262,7 @@ inline int lsd_sort_pairs(uint32_t *k0, int32_t *v0, uint32_t *k1, int32_t *v1, 
     else
       hipLaunchKernelGGL((lsd::hist_kernel<16, lsd::RADIX>), dim3((unsigned)nt), dim3(lsd::NT), 0,
                          st, ki, n, n_dev, shift, mask, hist, nt);
-    hipLaunchKernelGGL(lsd::scan_kernel, dim3((unsigned)radix), dim3(lsd::NT), 0, st, hist, nt,
+    hipLaunchKernelGGL(lsd::scan_kernel, dim3((unsigned)radix), dim3(1024), 0, st, hist, nt,
                        totals, n_dev, n, (int64_t)lsd::NT * ipt);
     const bool fin = fo && shift + dbits >= end_bit;
     const lsd::FinalOut f = fin ? *fo : lsd::FinalOut{nullptr, nullptr, nullptr};
@@ -336,7 +298,7 @@ inline const uint32_t *lsd_one_pass(const uint32_t *k0, const int32_t *v0, uint3
   do {                                                                                            \
     hipLaunchKernelGGL((lsd::hist_kernel<I, RX>), dim3((unsigned)nt), dim3(lsd::NT), 0, st, k0,   \
                        n, n_dev, 0, mask, hist, nt);                                              \
-    hipLaunchKernelGGL(lsd::scan_kernel, dim3((unsigned)RX), dim3(lsd::NT), 0, st, hist, nt,      \
+    hipLaunchKernelGGL(lsd::scan_kernel, dim3((unsigned)RX), dim3(1024), 0, st, hist, nt,         \
                        totals, n_dev, n, (int64_t)lsd::NT * I);                                   \
     hipLaunchKernelGGL((lsd::scatter_kernel<I, false, RX>), dim3((unsigned)nt), dim3(lsd::NT), 0, \
                        st, k0, v0, k1, v1, n, n_dev, 0, nbits, hist, totals, nt, none);           \

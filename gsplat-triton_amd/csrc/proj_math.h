@@ -12,9 +12,11 @@
 
 namespace gs {
 
-// the packed-count scan (projection.hip), also used by projection_covar.hip
-// and the 2DGS packed projection (surfel_projection.hip)
-void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st);
+// the count scan (projection.hip), also used by projection_covar.hip, the 2DGS
+// packed projection (surfel_projection.hip), ply.hip, tsdf.hip and
+// strategy.hip: exclusive scan in place of `rows` rows of nb counts each, row
+// r's total -> total[r]
+void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st, int rows = 1);
 
 struct Cam {
   M3 R;

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "geom_adam.h"
 #include "proj_math.h"
+#include "scan_ops.h"
 #include "wave_ops.h"
 #include "../../include/gsplat_hip.h"
 
@@ -74,40 +75,13 @@ __global__ void __launch_bounds__(256) projection_fwd_kernel(ProjFwdArgs a) {
   ewa_fwd_tail<MODE>(a, c, n, idx, keep, mc[2], p);
 }
 
-// Exclusive scan of the packed per-block counts in place, total -> total[0]
-// (one 1024-lane workgroup walking the C * blocks_per_row counts).
+// Exclusive scan of each row of nb per-block counts in place (workgroup r
+// scans row r), its total -> total[r]: one 1024-lane workgroup per row.
 __global__ void __launch_bounds__(1024) packed_scan_kernel(int64_t nb, int64_t *cnt,
                                                            int64_t *total) {
   __shared__ int64_t wave_tot[16];
-  __shared__ int64_t chunk_tot;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = i < nb ? cnt[i] : 0;
-    int64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wave_tot[wid] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int64_t run = 0;
-      for (int w = 0; w < 16; ++w) {
-        const int64_t t = wave_tot[w];
-        wave_tot[w] = run;
-        run += t;
-      }
-      chunk_tot = run;
-    }
-    __syncthreads();
-    if (i < nb) cnt[i] = carry + wave_tot[wid] + x - v;
-    carry += chunk_tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) total[0] = carry;
+  const int64_t sum = array_exclusive_scan<int64_t, 1, true>(cnt + blockIdx.x * nb, nb, wave_tot);
+  if (threadIdx.x == 0) total[blockIdx.x] = sum;
 }
 
 struct ProjBwdArgs {
@@ -610,9 +584,10 @@ extern "C" int gsplat_hip_projection_bwd_adam_pose(
 }
 
 namespace gs {
-// the packed-count scan, shared with the 2DGS packed projection (surfel_projection.hip)
-void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st) {
-  hipLaunchKernelGGL(packed_scan_kernel, dim3(1), dim3(1024), 0, st, nb, cnt, total);
+// the count scan, shared with the 2DGS packed projection (surfel_projection.hip),
+// PLY rows, marching cubes and densification (strategy.hip: one row per list)
+void launch_packed_scan(int64_t nb, int64_t *cnt, int64_t *total, hipStream_t st, int rows) {
+  hipLaunchKernelGGL(packed_scan_kernel, dim3(rows), dim3(1024), 0, st, nb, cnt, total);
 }
 }  // namespace gs
 
@@ -646,8 +621,7 @@ extern "C" int gsplat_hip_projection_packed_count(int C, int N, const float *mea
   a.block_cnt = reinterpret_cast<int64_t *>(workspace);
   dim3 grid((N + 255) / 256, C);
   hipLaunchKernelGGL(projection_fwd_kernel<1>, grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL(packed_scan_kernel, dim3(1), dim3(1024), 0, st,
-                     (int64_t)grid.x * grid.y, a.block_cnt, nnz_device);
+  gs::launch_packed_scan((int64_t)grid.x * grid.y, a.block_cnt, nnz_device, st);
   GS_CHECK_LAUNCH("projection_packed_count");
   return 0;
 }

@@ -5,6 +5,7 @@
 // tile, or per 2x2 group for the XCDs), its plan with split heavy tiles, and
 // the backward's work items.
 #include "raster16.h"
+#include "scan_ops.h"
 #include "../../include/gsplat_hip.h"
 
 #include <stdlib.h>
@@ -45,35 +46,12 @@ GS_INLINE int bucket_of(int64_t n) { return n >= 2048 ? 0 : n >= 1024 ? 1 : n >=
 // (at most 16384 items in all), so that one scan serves the four buckets.
 GS_INLINE uint64_t bucket_one(int bk) { return (uint64_t)1 << (16 * bk); }
 
-// Exclusive scan over the workgroup's 1024 lanes: a wave scan, then the 16
-// waves' sums through `wsum`.  v: the lane's value on entry, the sum over the
-// lanes before it on return; returns the total.  One barrier.
-template <class T>
-GS_INLINE T block_scan(T &v, T (&wsum)[16]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  T before = 0, total = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    before += i < w ? wsum[i] : 0;
-    total += wsum[i];
-  }
-  v = before + (x - v);
-  return total;
-}
-
 // From a lane's packed bucket counts: pos[bk], the place of its first item of
 // bucket bk in the order (the buckets one after the other, heaviest first);
 // returns the number of items.
 GS_INLINE int bucket_starts(uint64_t mine, uint64_t (&wsum)[16], int (&pos)[4]) {
-  const uint64_t total = block_scan(mine, wsum);
+  uint64_t total;
+  mine = block_exclusive_scan(mine, wsum, total);
   int base = 0;
 #pragma unroll
   for (int bk = 0; bk < 4; ++bk) {
@@ -229,7 +207,8 @@ fwd_plan_kernel(int n_tiles, const int32_t *__restrict__ offsets, int64_t n_isec
   block_max_out(nmax, max_out);
   int pos[4];
   const int n_whole = bucket_starts(mine, wsum, pos);
-  const int n_chunks = block_scan(cpos, csum);
+  int n_chunks;
+  cpos = block_exclusive_scan(cpos, csum, n_chunks);
   for (int i = 0; i < PER; ++i) {
     const int t = tid + 1024 * i;
     if (t >= n_tiles) break;
@@ -273,15 +252,7 @@ chunk_items_kernel(int n_tiles, const int32_t *__restrict__ offsets, int64_t n_i
     nf = (int)(n / L);
     nt = (n % L) != 0;
   }
-  int xf = nf, xt = nt;  // inclusive wave scans
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int yf = __shfl_up(xf, o, 64), yt = __shfl_up(xt, o, 64);
-    if (lane >= o) {
-      xf += yf;
-      xt += yt;
-    }
-  }
+  const int xf = wave_inclusive_scan(nf), xt = wave_inclusive_scan(nt);
   int bf = 0, bt = 0;
   if (lane == 63) {
     bf = xf ? atomicAdd(&n_items[0], xf) : 0;

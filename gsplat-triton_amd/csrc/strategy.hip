@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "proj_math.h"  // launch_packed_scan
 #include "../../include/gsplat_hip.h"
 
 namespace gs {
@@ -215,43 +216,6 @@ densify_plan_kernel(int64_t N, const float *__restrict__ grad2d, const float *__
     for (int q = 0; q < kDB / 64; ++q) t += wcnt[threadIdx.x][q];
     block_counts[threadIdx.x * nb + blockIdx.x] = t;
   }
-}
-
-// Exclusive scan of each of the kRows block-count rows (workgroup k scans row k);
-// its total goes to totals[k].
-__global__ void __launch_bounds__(1024)
-densify_scan_kernel(int64_t nb, int64_t *__restrict__ block_counts, int64_t *__restrict__ totals) {
-  int64_t *row = block_counts + blockIdx.x * nb;
-  __shared__ int64_t wave_tot[16];
-  __shared__ int64_t chunk_tot;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = (i < nb) ? row[i] : 0;
-    int64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wave_tot[wid] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int64_t run = 0;
-      for (int q = 0; q < 16; ++q) {
-        const int64_t t = wave_tot[q];
-        wave_tot[q] = run;
-        run += t;
-      }
-      chunk_tot = run;
-    }
-    __syncthreads();
-    if (i < nb) row[i] = carry + wave_tot[wid] + x - v;
-    carry += chunk_tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
 constexpr int kMaxArrays = 24;
@@ -511,8 +475,8 @@ extern "C" int gsplat_hip_densify_plan(int64_t N, const float *grad2d, const flo
   hipLaunchKernelGGL(strat::densify_plan_kernel, dim3((unsigned)nb), dim3(strat::kDB), 0, st, N,
                      grad2d, count, log_scales, logits, radii2d, cfg, flags, bc, nb);
   GS_CHECK_LAUNCH("densify_plan");
-  hipLaunchKernelGGL(strat::densify_scan_kernel, dim3(strat::kRows), dim3(1024), 0, st, nb, bc,
-                     totals);
+  // exclusive scan of each of the kRows block-count rows, row k's total -> totals[k]
+  gs::launch_packed_scan(nb, bc, totals, st, strat::kRows);
   GS_CHECK_LAUNCH("densify_scan");
   return 0;
 }

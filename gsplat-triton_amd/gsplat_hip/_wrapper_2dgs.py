@@ -121,9 +121,10 @@ class _FullyFusedProjectionPacked2DGS(torch.autograd.Function):
         depths = torch.empty(nnz, device=dev)
         ray_transforms = torch.empty((nnz, 3, 3), device=dev)
         normals = torch.empty((nnz, 3), device=dev)
-        _lib.call("gsplat_hip_projection_2dgs_packed_fwd", C, N, *args, _ptr(ws),
-                  _ptr(camera_ids), _ptr(gaussian_ids), _ptr(radii), _ptr(means2d),
-                  _ptr(depths), _ptr(ray_transforms), _ptr(normals), _stream())
+        if nnz > 0:  # every pair culled: empty outputs have null pointers, which the entry refuses
+            _lib.call("gsplat_hip_projection_2dgs_packed_fwd", C, N, *args, _ptr(ws),
+                      _ptr(camera_ids), _ptr(gaussian_ids), _ptr(radii), _ptr(means2d),
+                      _ptr(depths), _ptr(ray_transforms), _ptr(normals), _stream())
         ctx.save_for_backward(camera_ids, gaussian_ids, means, quats, scales, viewmats, Ks,
                               ray_transforms)
         ctx.width, ctx.height, ctx.sparse_grad = int(width), int(height), sparse_grad

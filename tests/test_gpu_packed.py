@@ -113,3 +113,59 @@ def test_rasterization_packed_matches_dense(C, mode):
     torch.testing.assert_close(ra1, ra0, rtol=1e-5, atol=1e-5)
     for a, b in zip(g1, g0):
         torch.testing.assert_close(a, b, rtol=1e-3, atol=1e-4 * float(b.abs().max()))
+
+
+# ------------------------------------------------- the count scan's rounds
+# packed projection counts 256 Gaussians per block and scans the block counts
+# 1024 per round: one block fewer than a round, a round, one block into the
+# second; then one lane, a wave boundary and a workgroup boundary
+SCAN_SIZES = [256 * 1023, 256 * 1024, 256 * 1024 + 1, 1, 63, 64, 65, 255, 256, 257]
+
+
+def sparse_scene(N, n_vis, seed=0):
+    """N Gaussians behind the camera but n_vis scattered ones, the first and
+    the last among them; returns the inputs and the sorted visible indices."""
+    g = torch.Generator().manual_seed(seed)
+    vis = torch.randperm(N, generator=g)[:n_vis]
+    if n_vis:
+        vis = torch.unique(torch.cat([vis, torch.tensor([0, N - 1])]))  # sorted
+    means = torch.zeros(N, 3)
+    means[:, 2] = -5.0
+    means[vis] = torch.randn(len(vis), 3, generator=g) * 0.3 + torch.tensor([0.0, 0.0, 4.0])
+    quats = torch.zeros(N, 4)
+    quats[:, 0] = 1.0
+    scales = torch.full((N, 3), 0.05)
+    vm = torch.eye(4)[None]
+    K = torch.tensor([[150.0, 0, 80], [0, 150.0, 60], [0, 0, 1]])[None]
+    return [x.to(DEV) for x in (means, quats, scales, vm, K)] + [160, 120], vis.to(DEV)
+
+
+def _packed_ids_are_nonzero_of_dense(project, N, n_vis):
+    (means, quats, scales, vm, K, W, H), vis = sparse_scene(N, n_vis)
+    radii = project(means, quats, scales, vm, K, W, H, False)[0]
+    cid, gid = project(means, quats, scales, vm, K, W, H, True)[:2]
+    nz = torch.nonzero(radii > 0)
+    assert torch.equal(nz[:, 1], vis)  # the scene is what it says
+    assert cid.numel() == nz.shape[0] == len(vis)
+    assert torch.equal(cid, nz[:, 0]) and torch.equal(gid, nz[:, 1])
+
+
+def _project_3dgs(means, quats, scales, vm, K, W, H, packed):
+    from gsplat_hip import fully_fused_projection
+    return fully_fused_projection(means, None, quats, scales, vm, K, W, H, packed=packed)
+
+
+def _project_2dgs(means, quats, scales, vm, K, W, H, packed):
+    from gsplat_hip import fully_fused_projection_2dgs
+    return fully_fused_projection_2dgs(means, quats, scales, vm, K, W, H, packed=packed)
+
+
+@pytest.mark.parametrize("project", [_project_3dgs, _project_2dgs], ids=["3dgs", "2dgs"])
+@pytest.mark.parametrize("N", SCAN_SIZES)
+def test_packed_count_scan_rounds(project, N):
+    _packed_ids_are_nonzero_of_dense(project, N, min(N, 300))
+
+
+@pytest.mark.parametrize("project", [_project_3dgs, _project_2dgs], ids=["3dgs", "2dgs"])
+def test_packed_count_all_invisible(project):
+    _packed_ids_are_nonzero_of_dense(project, 257, 0)

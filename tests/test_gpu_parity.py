@@ -802,3 +802,85 @@ def test_full_size_invariants_m3():
             scale = max(1e-12, float(b.abs().max()))
             close_most(a, b, 1e-3, 1e-4 * scale, name, max_frac=2e-3, rows=True,
                        out_bound=0.05 * scale)
+
+
+# ------------------------------------------------- isect: the scans' rounds
+def _lsd_tile_items():
+    """Items per tile of the LSD sort's large inputs, from lsd_sort.h."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(__file__), "..", "gsplat-triton_amd", "csrc",
+                            "lsd_sort.h")).read()
+    nt = int(re.search(r"constexpr int NT = (\d+);", src).group(1))
+    ipt = int(re.search(r"pick_ipt\(int64_t n\) \{ return n <= .*\? \d+ : (\d+); \}", src).group(1))
+    return nt * ipt
+
+
+def _sparse_isect_input(G, on, rmax, seed=0):
+    """[1, G] isect inputs: radius 0 except at the indices `on`."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    ts, tw, th = 16, 120, 68
+    on = torch.as_tensor(sorted({int(i) for i in on if 0 <= int(i) < G}), device=DEV)
+    m2 = torch.rand(1, G, 2, device=DEV, generator=g) * torch.tensor([tw * ts, th * ts], device=DEV)
+    r = torch.zeros(1, G, dtype=torch.int32, device=DEV)
+    if len(on):
+        r[0, on] = torch.randint(1, rmax + 1, (len(on),), device=DEV, generator=g).int()
+    d = torch.rand(1, G, device=DEV, generator=g) * 10 + 0.1
+    d[:, ::3] = 1.0  # ties: the sort's stability shows
+    return m2, r, d, ts, tw, th
+
+
+def _check_isect_against_torch(m2, r, d, ts, tw, th, min_isects=0):
+    """tiles_per_gauss sums to n_isects; unsorted: Gaussian-major ids; sorted,
+    under every strategy: the stable torch sort of the unsorted ids."""
+    import gsplat_hip
+    from gsplat_hip import _wrapper
+    G = r.numel()
+    tpg, ids_u, fids_u = gsplat_hip.isect_tiles(m2, r, d, ts, tw, th, sort=False)
+    n = ids_u.numel()
+    assert int(tpg.sum()) == n == fids_u.numel() and n >= min_isects
+    assert torch.equal((tpg > 0).flatten(), (r > 0).flatten())
+    assert torch.equal(fids_u.long(),
+                       torch.repeat_interleave(torch.arange(G, device=DEV), tpg.flatten().long()))
+    order = torch.sort(ids_u, stable=True).indices
+    old = _wrapper.ISECT_SORT
+    try:
+        for mode in ("tile_first", "depth_first", "full"):
+            _wrapper.ISECT_SORT = mode
+            tpg_s, ids, fids = gsplat_hip.isect_tiles(m2, r, d, ts, tw, th, sort=True)
+            assert torch.equal(tpg_s, tpg), mode
+            assert torch.equal(ids, ids_u[order]) and torch.equal(fids, fids_u[order]), mode
+    finally:
+        _wrapper.ISECT_SORT = old
+
+
+@pytest.mark.parametrize("G", [256 * 8192 - 1, 256 * 8192 + 257])
+def test_isect_block_scan_rounds(G):
+    """The count kernel sums 256 Gaussians per block and the block scan takes
+    8192 block sums per round: just under a round, and a block and a lane
+    into the second, with ~1000 Gaussians on, both ends and both sides of the
+    round boundary among them."""
+    rng = np.random.default_rng(G)
+    B = 256 * 8192
+    on = list(rng.choice(G, 1000, replace=False)) + [0, G - 1, B - 1, B, B + 256]
+    _check_isect_against_torch(*_sparse_isect_input(G, on, rmax=40))
+
+
+def test_isect_lsd_scan_second_round():
+    """More isects than 1024 tiles of the LSD sort hold: its histogram scan
+    (one 1024-lane workgroup per digit) takes a second round."""
+    need = 1024 * _lsd_tile_items() + 1
+    G = 700  # each Gaussian on all 120 x 68 tiles
+    m2, r, d, ts, tw, th = _sparse_isect_input(G, range(G), rmax=1)
+    r[:] = 4000
+    assert G * tw * th >= need
+    _check_isect_against_torch(m2, r, d, ts, tw, th, min_isects=need)
+
+
+@pytest.mark.parametrize("G", [1, 63, 64, 65, 255, 256, 257])
+def test_isect_workgroup_scan_edges(G):
+    """One lane, a wave boundary and a workgroup boundary, every Gaussian on;
+    then none on (every total 0)."""
+    _check_isect_against_torch(*_sparse_isect_input(G, range(G), rmax=40))
+    m2, r, d, ts, tw, th = _sparse_isect_input(G, [], rmax=40)
+    _check_isect_against_torch(m2, r, d, ts, tw, th)

@@ -98,3 +98,46 @@ def test_refine_large_matches_oracle():
             np.testing.assert_array_equal(got, rp[k], err_msg=k)
         np.testing.assert_array_equal(m[k][0].cpu().numpy(), rm[k][0], err_msg=k)
         np.testing.assert_array_equal(m[k][1].cpu().numpy(), rm[k][1], err_msg=k)
+
+
+def test_refine_scan_second_round_matches_oracle():
+    """256 * 1024 + 1 Gaussians: the scan of the per-block counts (1024 blocks
+    of 256 per round) goes one block into its second round.  A few hundred
+    Gaussians split, duplicate or are pruned, at both ends of the array and
+    scattered between; the compaction equals the oracle's."""
+    from gsplat_hip import densify
+    from oracle import strategy_oracle as S
+    gen = torch.Generator().manual_seed(9)
+    N = 256 * 1024 + 1
+    params = {"means": torch.randn(N, 3, generator=gen),
+              "scales": torch.rand(N, 3, generator=gen) * 3.0 - 6.9,  # below prune_scale3d
+              "quats": torch.randn(N, 4, generator=gen),
+              "opacities": torch.full((N,), 2.0),
+              "sh0": torch.randn(N, 1, 3, generator=gen)}
+    moms = {k: [torch.rand(v.shape, generator=gen), torch.rand(v.shape, generator=gen)]
+            for k, v in params.items()}
+    ends = torch.cat([torch.arange(0, 40), torch.arange(N - 40, N)])
+    grow = torch.cat([ends[::2], torch.randperm(N, generator=gen)[:300]])
+    prune = torch.cat([ends[1::2], torch.randperm(N, generator=gen)[:100]])
+    count = torch.ones(N)
+    grad2d = torch.zeros(N)
+    grad2d[grow] = 1e-3  # above grow_grad2d: split or duplicate by scale
+    params["opacities"][prune] = -8.0  # below prune_opa
+    cfg = densify.DefaultStrategyConfig()
+    dg = torch.Generator(device=DEV).manual_seed(11)
+    dp = {k: v.to(DEV) for k, v in params.items()}
+    dm = {k: [t.to(DEV) for t in v] for k, v in moms.items()}
+    p, m, c = densify.refine(dp, dm, grad2d.to(DEV), count.to(DEV), 3500, cfg, generator=dg)
+    z = torch.randn(2, c[1], 3, device=DEV, generator=torch.Generator(device=DEV).manual_seed(11))
+    rp, rm, rc = S.refine({k: v.numpy() for k, v in params.items()},
+                          {k: (a.numpy(), b.numpy()) for k, (a, b) in moms.items()},
+                          grad2d.numpy(), count.numpy(), 3500, z.cpu().numpy())
+    assert c == rc and all(50 <= n <= 500 for n in rc), rc
+    for k in params:
+        got = p[k].cpu().numpy()
+        if k in ("means", "scales"):
+            np.testing.assert_allclose(got, rp[k], rtol=2e-6, atol=1e-6, err_msg=k)
+        else:
+            np.testing.assert_array_equal(got, rp[k], err_msg=k)
+        np.testing.assert_array_equal(m[k][0].cpu().numpy(), rm[k][0], err_msg=k)
+        np.testing.assert_array_equal(m[k][1].cpu().numpy(), rm[k][1], err_msg=k)
