@@ -7,7 +7,8 @@ CPU, written apart from gsplat_hip/losses.py:
 with the SSIM of train_step.ssim (11x11 Gaussian window, sigma 1.5, "valid"
 region, C1 = 0.01^2, C2 = 0.03^2).  loss_and_grads returns L, dL/dc and dL/da
 by autograd; closed_forms returns the same two gradients from u = dL/dx as
-m ? u : 0 and -sum_ch b_ch u_ch."""
+m ? u : 0 and -sum_ch b_ch u_ch.  ssim_and_l1 / ssim_and_l1_grads: the two means
+(S, L1) on their own and the gradient of a S + b L1 (tests/loss_cases.py)."""
 
 import torch
 import torch.nn.functional as F
@@ -53,6 +54,45 @@ def loss_of(x, y, lam):
     return (1.0 - lam) * (x - y).abs().mean() + lam * (1.0 - ssim_valid(x, y))
 
 
+def ssim_and_l1(x, y):
+    """(mean SSIM over the valid region, mean |x - y|) of [B,H,W,C] float64 images."""
+    return ssim_valid(x, y), (x - y).abs().mean()
+
+
+def ssim_rounding_floor(x, y):
+    """First-order worst case of the mean SSIM's error when the window sums
+    are float32 fma chains (tests/loss_cases.py derives it): each statistic is
+    11 horizontal and 11 vertical roundings on its 121 non-negative-weighted
+    terms, one more where the term is a product, so with u = 2^-24
+        d E[x^2] <= 23u E[x^2],  d mu <= 22u E|x|,  d mu1 mu2 <= 45u E|x| E|y|,
+        d s11 <= 23u E[x^2] + 45u E|x|^2 (+ u |s11| for the subtraction), ...
+    carried through SSIM = A1 A2 / (B1 B2) relative to each factor, plus 4u
+    for the quotient itself."""
+    u = 2.0 ** -24
+    x, y = x.permute(0, 3, 1, 2), y.permute(0, 3, 1, 2)
+    C = x.shape[1]
+    w = _window()
+    wx = w.view(1, 1, 1, -1).repeat(C, 1, 1, 1)
+    wy = w.view(1, 1, -1, 1).repeat(C, 1, 1, 1)
+
+    def blur(t):
+        return F.conv2d(F.conv2d(t, wx, groups=C), wy, groups=C)
+
+    m1, m2, a1, a2 = blur(x), blur(y), blur(x.abs()), blur(y.abs())
+    e11, e22, e12, a12 = blur(x * x), blur(y * y), blur(x * y), blur((x * y).abs())
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    s11, s22, s12 = e11 - m1 * m1, e22 - m2 * m2, e12 - m1 * m2
+    A1, A2 = 2 * m1 * m2 + C1, 2 * s12 + C2
+    B1, B2 = m1 * m1 + m2 * m2 + C1, s11 + s22 + C2
+    d11 = 23 * u * e11 + 45 * u * a1 * a1 + u * s11.abs()
+    d22 = 23 * u * e22 + 45 * u * a2 * a2 + u * s22.abs()
+    d12 = 23 * u * a12 + 45 * u * a1 * a2 + u * s12.abs()
+    rel = (2 * 45 * u * a1 * a2 + u * A1.abs()) / A1.abs() \
+        + (45 * u * (a1 * a1 + a2 * a2) + 2 * u * B1) / B1 \
+        + (2 * d12 + u * A2.abs()) / A2.abs() + (d11 + d22 + 2 * u * B2) / B2 + 4 * u
+    return ((A1 * A2 / (B1 * B2)).abs() * rel).mean()
+
+
 def _f64(t):
     return None if t is None else t.detach().double().cpu()
 
@@ -71,6 +111,14 @@ def loss_and_grads(c, y, lam, m=None, a=None, b=None, scale=1.0):
     L = loss_of(compose(c, m, a, b), y, lam)
     (scale * L).backward()
     return L.detach(), c.grad, (a.grad if b is not None else None)
+
+
+def ssim_and_l1_grads(x, y, a, b):
+    """(S, L1, d(a S + b L1)/dx), float64, by autograd."""
+    x, y = _f64(x).requires_grad_(True), _f64(y)
+    S, L1 = ssim_and_l1(x, y)
+    (a * S + b * L1).backward()
+    return S.detach(), L1.detach(), x.grad
 
 
 def closed_forms(c, y, lam, m=None, a=None, b=None):
