@@ -29,6 +29,7 @@ from .compression import PngCompression
 from .contributions import contribution_scores, prune_splats, rasterize_to_contributions
 from .depth_loss import sparse_depth_loss
 from .io import load_ply, save_ply
+from .knn import knn
 from .losses import geometry_loss_2dgs
 from .mesh import TSDFVolume, save_mesh_ply
 from .pose import pose_adjust
@@ -80,5 +81,6 @@ __all__ = [
     "rasterize_to_contributions",
     "contribution_scores",
     "prune_splats",
+    "knn",
 ]
 __version__ = "0.1.0"

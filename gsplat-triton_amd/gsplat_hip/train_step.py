@@ -114,6 +114,7 @@ from .densify import DefaultStrategyConfig
 from . import mcmc as _mcmc
 from .mcmc import MCMCStrategyConfig
 from .color_correct import color_correct as _color_correct
+from .knn import knn as _knn
 from .losses import FusedAdam, l1_ssim_loss, ssim_and_l1
 from . import _lib, _wrapper
 from .appearance import AppearanceOptimizer
@@ -162,10 +163,20 @@ def camera_pool(viewmats, Ks, src_w, src_h, width, height, n, seed=0):
     return torch.stack(vms), torch.stack(ks)
 
 
-def knn_log_scales(points: torch.Tensor, init_scale: float = 1.0) -> torch.Tensor:
+def knn_log_scales(points: torch.Tensor, init_scale: float = 1.0,
+                   backend: str = "host") -> torch.Tensor:
     """log of the RMS distance to the 3 nearest neighbours, repeated over the
     3 axes (simple_trainer.py:221-224 with examples/utils.py:141-151 knn):
-    the SfM initialisation's scales.  One-off host work (a k-d tree)."""
+    the SfM initialisation's scales.  backend="host": one-off host work (a
+    k-d tree).  backend="hip": gsplat_hip.knn on the points' device (csrc/
+    knn.hip), the same formula on its float32 distances; the result stays on
+    that device."""
+    if backend == "hip":
+        d, _ = _knn(points.detach().float().contiguous(), 4)
+        dist2_avg = (d[:, 1:].double() ** 2).mean(-1).float()
+        return torch.log(torch.sqrt(dist2_avg) * init_scale).unsqueeze(-1).repeat(1, 3)
+    if backend != "host":
+        raise ValueError(f"knn_log_scales: backend 'host' or 'hip', got {backend!r}")
     from scipy.spatial import cKDTree
     pts = points.detach().cpu().double().numpy()
     d, _ = cKDTree(pts).query(pts, k=4, workers=-1)
@@ -273,6 +284,7 @@ _REFUSALS = {
     "mesh": ("one-GPU trainers only", _MANY),
     "scores": ("one-GPU 3DGS trainers without app_opt only",
                ("model='2dgs'", "app_opt") + _MANY),
+    "init_knn='hip'": ("the search runs on a GPU device only", ("a CPU device",)),
 }
 
 
@@ -342,9 +354,16 @@ class Trainer:
                  pose_noise: float = 0.0, depth_loss: bool = False, depth_lambda: float = 1e-2,
                  depth_points=None, app_opt: bool = False, app_embed_dim: int = 16,
                  app_opt_lr: float = 1e-3, app_opt_reg: float = 1e-6,
-                 masks: Optional[torch.Tensor] = None, random_bkgd: bool = False):
+                 masks: Optional[torch.Tensor] = None, random_bkgd: bool = False,
+                 init_knn: str = "host"):
         assert model in ("3dgs", "2dgs"), model
         assert init in ("random", "sfm"), init
+        # init="sfm": where the neighbour search behind the initial scales runs
+        # (knn_log_scales): "host", a k-d tree, or "hip", gsplat_hip.knn on `device`
+        if init_knn not in ("host", "hip"):
+            raise ValueError(f"init_knn: 'host' or 'hip', got {init_knn!r}")
+        if init_knn == "hip":
+            _refuse("init_knn='hip'", {"a CPU device": torch.device(device).type != "cuda"})
         # the options of the one-GPU dense trainer, each refused with what it
         # does not run with (_REFUSALS) before any device work
         env = os.environ.get
@@ -464,7 +483,10 @@ class Trainer:
             if not self.app_opt:  # (the last draw: the geometry is a plain trainer's)
                 sh[:, 1:, :] = torch.randn(N, K - 1, 3, generator=g) * 0.01
         else:  # simple_trainer.create_splats_with_optimizers, init_type="sfm"
-            scales = knn_log_scales(points, init_scale)
+            if init_knn == "hip":
+                scales = knn_log_scales(points.to(device), init_scale, backend="hip").cpu()
+            else:
+                scales = knn_log_scales(points, init_scale)
             quats = torch.rand(N, 4, generator=g)
             opac = torch.logit(torch.full((N,), float(init_opacity)))
         self.params = {

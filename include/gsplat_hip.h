@@ -77,7 +77,9 @@ const char *gsplat_hip_last_error(void);
  *     (similarity transforms of splat scenes);
  *     gsplat_hip_rasterize_score (per-Gaussian contribution scores);
  *     gsplat_hip_rasterize_wide_supported / _fwd / _bwd (the wide-channel
- *     rasterizer: 33..512 channels blended on the matrix cores). */
+ *     rasterizer: 33..512 channels blended on the matrix cores);
+ *     gsplat_hip_knn and gsplat_hip_knn_workspace_bytes (exact k-nearest
+ *     neighbours of a point cloud). */
 int gsplat_hip_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -1629,6 +1631,35 @@ int gsplat_hip_splat_xform_rotate_sh(int64_t N, int degree, int64_t S, const flo
                                      const int32_t *status, const int64_t *segment_ids,
                                      const float *shN, float *out_shN, int64_t *counter,
                                      void *stream);
+
+/* ---------------------------------------------------------------------------
+ * k-nearest neighbours (ABI 38, new entries only; examples/utils.py:141 knn,
+ * csrc/knn.hip): the k nearest of points[N,3] for every row of queries[M,3],
+ * 1 <= N <= 2^30, 0 <= M <= 2^30, 1 <= k <= min(32, N); otherwise status 1.
+ * queries = NULL: the points are their own queries (M is ignored, N rows come
+ * back, each point among its own neighbours at distance 0).
+ *
+ * Row i of idx[M,k] (int64) holds the k points in ascending order of
+ * (d2, index), d2 = ((dx*dx) + (dy*dy)) + (dz*dz) evaluated in float64 on the
+ * float32 coordinates, every product and sum rounded (no FMA), the lower index
+ * first on a tie; dists[M,k] = (float)sqrt(d2).  The order is defined exactly,
+ * so the result equals a brute-force float64 search and is the same bits in
+ * every run.  Non-finite coordinates give unspecified neighbours, but every
+ * index lies in [0, N) and the search ends: its level walk is bounded by
+ * construction.
+ *
+ * The points are sorted once by a 60-bit Morton key of their cells in a 2^20
+ * grid over their bounding box (two lsd_sort_pairs runs); every coarser grid
+ * is a prefix of the same order, and each query climbs the levels until its
+ * k-th distance lies inside its 3x3x3 block of cells.
+ *   workspace = gsplat_hip_knn_workspace_bytes(N, M) bytes of uninitialised
+ *   memory, 16-B aligned (M = 0 for queries = NULL; 0 is returned for sizes
+ *   out of range): keys, permutations, sorted records and the sort's scratch.
+ * Nothing is allocated and the host reads nothing back: every launch goes on
+ * `stream`, and the call can be captured. */
+int64_t gsplat_hip_knn_workspace_bytes(int64_t N, int64_t M);
+int gsplat_hip_knn(int64_t N, const float *points, int64_t M, const float *queries, int k,
+                   float *dists, int64_t *idx, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Progress watchdog (ABI 34; csrc/watchdog.cpp).  A native thread that ends
