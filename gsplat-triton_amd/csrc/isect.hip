@@ -589,7 +589,10 @@ static int isect_write_sorted_impl(
     return gsplat_hip_isect_offsets(cnt_dev ? n_isects : (n_visible > 0 ? n_isects : 0), cnt_dev,
                                     isect_ids, n_cameras, tile_width, tile_height, offsets, st);
   };
-  if (n_isects <= 0 || n_visible <= 0) return plain_offsets();
+  // capacity 0 with rank buffers: an overflow like any other, the depth ranks
+  // are still written (rect_kernel) -- the depth sort and that kernel only
+  const bool ranks_only = n_isects <= 0 && n_visible > 0 && cnt_dev && vis_rank;
+  if ((n_isects <= 0 || n_visible <= 0) && !ranks_only) return plain_offsets();
   const int key_bits = tile_bits + cam_bits;
   const SortedLayout L = sorted_layout(n_visible, n_isects, key_bits);
   GS_REQUIRE(workspace_bytes >= (int64_t)L.total, "isect_write_sorted: workspace %lld < %lld",
@@ -633,6 +636,10 @@ static int isect_write_sorted_impl(
     int32_t *n_huge = sc ? reinterpret_cast<int32_t *>(ws + L.nbig) : nullptr;
     hipLaunchKernelGGL(st::rect_kernel, dim3((unsigned)nbV), dim3(256), 0, st, n_visible, cnt_dev,
                        Vs, dks, means2d, radii, tile_size, geo, rect, blk, vis_rank, n_huge);
+    if (ranks_only) {
+      GS_CHECK_LAUNCH("isect_write_sorted (ranks)");
+      return plain_offsets();
+    }
     hipLaunchKernelGGL(isect_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, nbV, blk, nullptr,
                        nullptr);
     hipLaunchKernelGGL(st::emit_kernel, dim3((unsigned)nbV), dim3(256), 0, st, n_visible, cnt_dev,

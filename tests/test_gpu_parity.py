@@ -183,9 +183,12 @@ def test_isect_random_vs_oracle_large_radii(isect_mode):
 
 
 def test_isect_huge_gaussians_vs_oracle(isect_mode):
-    """Gaussians covering thousands of tiles (the grid-wide emission path,
-    > 1024 tiles), many of them adjacent in depth order, some with negative
-    depth (all-ones key), mixed with small ones: exact."""
+    """Gaussians covering thousands of tiles, many of them adjacent in depth
+    order, some with negative depth (all-ones key), mixed with small ones:
+    exact.  Its 2 x 69 x 57 tiles take the supertile expansion (isect_st.h),
+    where such a Gaussian is a few hundred (supertile, Gaussian) pairs; the
+    depth-first emission's grid-wide class (> 1024 tiles) it was written for
+    runs in tests/test_gpu_isect_matrix.py (legacy_t4, legacy_c8)."""
     import gsplat_hip
     from oracle import gsplat_oracle as O
     rng = np.random.default_rng(7)
